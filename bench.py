@@ -1,7 +1,19 @@
-"""Headline benchmark: ONE compact JSON line (the last line of stdout, < 4 KB: every contract key, `roofline`,
-`cpu_baseline`, `verified` {all_ok, checks, failed}, one or two numbers per secondary leg) + the full record in
-`bench_detail.json` next to this file and under gpurun_out/ (round 4: the one 21 KB line of round 3 did not fit the
+"""Headline benchmark: ONE compact JSON line (the last line of stdout, < 4 KB: every contract key, `roofline`, and
+with `--full` also `cpu_baseline`, `verified` {all_ok, checks, failed}, one or two numbers per secondary leg) + the
+full record in `bench_detail.json` next to this file (round 4: the one 21 KB line of round 3 did not fit the
 driver's 8 KB tail).  The objects described below are those of the FULL record.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: make the operands, warm up,
+time the K steps, write the outputs when `--dump-outputs DIR` asks for them, print the line (contract keys, `config`,
+`roofline`: both come out of the timed region itself).  Every other leg below -- `verified`, `cpu_baseline`, `svd`,
+`bond_sweep`, `dtype_sweep`, `mps_chain`, `mera`, `mera_chi64`, `helpers`, `gather_gemm`, `sliced_network` -- runs with
+`--full` only; the `--no-*` / `--svd-n 0` / `--rr-bond 0` / `--mera-chi 0` switches then drop single legs as before.
+
+`--dump-outputs DIR`: after the timed steps, what the LAST timed step returned -- the tensor of the node
+`contract_between` gave back -- goes to `DIR/contract_between.npy` (float32; ranks r > 0 of an N > 1 run:
+`contract_between_rank<r>.npy`).  Up to DUMP_FULL_BYTES the whole tensor; above that (D = 256: 4.3e9 entries) a fixed,
+seeded sample of its [i0, i1, :, :] slabs, `dump_slabs`, stacked in that order.  The operands come from the library's
+seeded generator, so two runs with the same arguments have the same inputs and two builds can be compared entry by entry.
 
 Workload at N=1 (BASELINE.json configs[1]): ``contract_between`` of two rank-4
 bf16 nodes with two shared bonds of dimension D=256 (layout L0: a[2]^b[0],
@@ -88,6 +100,14 @@ def parse_args(argv=None):
   p.add_argument("--gpus", type=int, default=1)
   p.add_argument("--steps", type=int, default=5)
   p.add_argument("--warmup", type=int, default=2)
+  p.add_argument("--full", action="store_true",
+                 help="after the headline, run every other leg too: value checks (verified), CPU baselines, bond / dtype "
+                      "sweeps, SVD, MERA, MPS chain, helper kernels, gather GEMM, the sliced network.  Without it the run "
+                      "is the headline alone and the switches that drop single legs (--no-*, --svd-n 0, ...) have nothing "
+                      "to act on")
+  p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                 help="write what the last timed step returned to DIR/<name>.npy (float32; a fixed seeded sample of slabs "
+                      "when the tensor is larger than DUMP_FULL_BYTES)")
   p.add_argument("--bond", type=int, default=256, help="bond dimension D of the rank-4 nodes")
   p.add_argument("--layout", default="L0", choices=["L0", "L1"])
   p.add_argument("--svd-n", type=int, default=4096, help="side of the split_node matrix (0 = skip)")
@@ -372,6 +392,35 @@ def verify_pair(*args, **kwargs):
 
 def host64(t):
   return np.asarray(t).astype(np.float64)
+
+
+DUMP_FULL_BYTES = 32 << 20     # of float32: a result up to this size is written whole, a larger one as a sample this large
+DUMP_SEED = 20
+
+
+def dump_slabs(shape):
+  """The (i0, i1) of the [i0, i1, :, :] slabs that stand for a rank-4 result too large to write whole: the first and the
+  last one (first / last tile row of the launch) and, between them, distinct ones drawn by a seeded generator, as many
+  as DUMP_FULL_BYTES of float32 hold, in ascending order.  A function of the shape alone: the same for every run."""
+  d0, d1 = int(shape[0]), int(shape[1])
+  n = max(2, min(d0 * d1, DUMP_FULL_BYTES // (4 * int(shape[2]) * int(shape[3]))))
+  inner = np.random.default_rng(DUMP_SEED).choice(np.arange(1, d0 * d1 - 1), size=n - 2, replace=False)
+  return [(int(f) // d1, int(f) % d1) for f in [0] + sorted(inner.tolist()) + [d0 * d1 - 1]]
+
+
+def dump_outputs(be, out, directory, rank=0):
+  """`--dump-outputs`: the tensor of the node the last timed step returned, as float32 (exact for bf16), whole or as the
+  slabs of `dump_slabs` (read back one by one: the D = 256 result is 8.6 GB on the device).  Returns the file's path."""
+  t = out.tensor
+  shape = tuple(int(s) for s in t.shape)
+  if 4 * int(np.prod(shape)) <= DUMP_FULL_BYTES:
+    arr = np.asarray(t)
+  else:
+    arr = np.stack([np.asarray(be.getitem(t, ij)) for ij in dump_slabs(shape)])
+  os.makedirs(directory, exist_ok=True)
+  path = os.path.join(directory, "contract_between.npy" if rank == 0 else f"contract_between_rank{rank}.npy")
+  np.save(path, np.ascontiguousarray(arr, dtype=np.float32))
+  return path
 
 
 def cpu_baseline(layout):
@@ -1444,6 +1493,8 @@ def main():
   args = parse_args()
   if args.gpus < 1:
     sys.exit("--gpus must be >= 1")
+  if args.steps < 1 or args.warmup < 0:
+    sys.exit("--steps must be >= 1 and --warmup >= 0")
   if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
     sys.exit(self_launch(args))       # no launcher around us: start the N ranks ourselves
   rank = int(os.environ.get("RANK", "0"))
@@ -1547,15 +1598,17 @@ def main():
                    "frac_at_observed_clock": (achieved / (BF16_MFMA_PEAK_TFLOPS * clock / MAX_CLOCK_MHZ)) if clock else None},
   }
   result["rccl_ranks"] = rccl_ranks(be, comm)
+  if args.dump_outputs:
+    dump_outputs(be, out, args.dump_outputs, rank)
   verified = {}
-  if rank == 0 and not args.no_verify and args.fill == "normal":
+  if args.full and rank == 0 and not args.no_verify and args.fill == "normal":
     try:
       verified["headline_D%d_%s" % (D, args.layout)] = verify_pair(be, A, B, out.tensor, args.layout, seed=1)
     except Exception as exc:  # pylint: disable=broad-except
       verified["headline"] = {"error": f"{type(exc).__name__}: {exc}"}
   del out, A, B
   ta.trim_pool()
-  if args.rr_bond > 0:
+  if args.full and args.rr_bond > 0:
     fenced(result, "sliced_network", lambda: sliced_network_bench(ta, be, comm, rank, world, args.rr_bond, args.rr_min_slices,
                                                                   not args.no_verify))
     if isinstance(result["sliced_network"], dict) and "verified" in result["sliced_network"]:
@@ -1565,7 +1618,7 @@ def main():
       fenced(result, "sliced_network_small", lambda: sliced_network_bench(ta, be, comm, rank, world, args.rr_bond_small,
                                                                           args.rr_min_slices, False))
   if rank == 0:
-    single = world == 1
+    single = world == 1 and args.full          # every secondary leg: one GPU, --full
     if single and not args.no_sweep:
       ta.trim_pool()
       try:

@@ -13,15 +13,24 @@ for p in (REPO, HERE):
     sys.path.insert(0, p)
 
 
+def _golden_parts():
+  """tests/golden/npz_parts.py (the fixture sets are stored as several archives of under 1 MiB each)."""
+  import importlib.util
+  spec = importlib.util.spec_from_file_location("npz_parts", os.path.join(HERE, "golden", "npz_parts.py"))
+  mod = importlib.util.module_from_spec(spec)
+  spec.loader.exec_module(mod)
+  return mod
+
+
 def pytest_configure(config):
   config.addinivalue_line("markers", "gpu: needs a real MI355X (run with `-m gpu` on the GPU box)")
 
 
 class Golden:
-  """tests/golden/golden.npz + cases.json (made by tests/golden/make_golden.py)."""
+  """tests/golden/golden.part*.npz + cases.json (made by tests/golden/make_golden.py)."""
 
   def __init__(self):
-    self.arrays = np.load(os.path.join(HERE, "golden", "golden.npz"))
+    self.arrays = _golden_parts().load(os.path.join(HERE, "golden", "golden"))
     with open(os.path.join(HERE, "golden", "cases.json")) as f:
       self.cases = json.load(f)
 
@@ -35,10 +44,10 @@ def golden():
 
 
 class GoldenLinalg(Golden):
-  """tests/golden/golden_linalg.npz + cases_linalg.json (made by make_golden_linalg.py)."""
+  """tests/golden/golden_linalg.part*.npz + cases_linalg.json (made by make_golden_linalg.py)."""
 
   def __init__(self):  # pylint: disable=super-init-not-called
-    self.arrays = np.load(os.path.join(HERE, "golden", "golden_linalg.npz"))
+    self.arrays = _golden_parts().load(os.path.join(HERE, "golden", "golden_linalg"))
     with open(os.path.join(HERE, "golden", "cases_linalg.json")) as f:
       self.cases = json.load(f)
 
@@ -49,10 +58,10 @@ def golden_linalg():
 
 
 class GoldenComplex(Golden):
-  """tests/golden/golden_complex.npz + cases_complex.json (made by make_golden_complex.py)."""
+  """tests/golden/golden_complex.part*.npz + cases_complex.json (made by make_golden_complex.py)."""
 
   def __init__(self):  # pylint: disable=super-init-not-called
-    self.arrays = np.load(os.path.join(HERE, "golden", "golden_complex.npz"))
+    self.arrays = _golden_parts().load(os.path.join(HERE, "golden", "golden_complex"))
     with open(os.path.join(HERE, "golden", "cases_complex.json")) as f:
       self.cases = json.load(f)
 

@@ -9,7 +9,7 @@ It imports google/TensorNetwork v0.4.6 from /root/reference with inert stubs for
 the absent h5py / graphviz (and ``opt_einsum`` -> tensornetwork_amd.pathfinder),
 drives its NumPy backend (``backends/numpy/numpy_backend.py``) through
 ``tn.ncon``, ``tn.contract_between``, ``tn.contract``, ``tn.split_node`` and the
-contractors, and stores inputs + outputs in ``tests/golden/golden.npz`` with the
+contractors, and stores inputs + outputs in ``tests/golden/golden.part*.npz`` with the
 case descriptions in ``tests/golden/cases.json``.  The fixtures are committed;
 the tests only read them.
 """
@@ -319,10 +319,11 @@ def main():
   gen_split()
   gen_contractors()
   gen_misc()
-  np.savez_compressed(os.path.join(HERE, "golden.npz"), **ARR)
+  import npz_parts  # pylint: disable=import-outside-toplevel
+  parts = npz_parts.save(os.path.join(HERE, "golden"), ARR)
   with open(os.path.join(HERE, "cases.json"), "w") as f:
     json.dump(CASES, f, indent=1, default=lambda o: o.tolist() if hasattr(o, "tolist") else str(o))
-  nbytes = os.path.getsize(os.path.join(HERE, "golden.npz"))
+  nbytes = sum(os.path.getsize(p) for p in parts)
   print(f"wrote {len(ARR)} arrays ({nbytes / 1e6:.2f} MB) and "
         f"{sum(len(v) for v in CASES.values() if isinstance(v, list))} cases")
 

@@ -1,5 +1,5 @@
 """Complex-dtype rows on the CPU: pins the oracle's svd / qr / rq / eigh / inv / expm
-against outputs of the reference itself on complex64 / complex128 inputs (tests/golden/golden_complex.npz)
+against outputs of the reference itself on complex64 / complex128 inputs (tests/golden/golden_complex.part*.npz)
 through the same checks the GPU suite applies to HipBackend."""
 import numpy as np
 

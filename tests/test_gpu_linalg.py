@@ -1,6 +1,6 @@
 """GPU parity for the decomposition / dense-linalg rows: HipBackend.qr / rq /
 eigh / inv / expm and the host layer's split_node_qr / split_node_rq against the reference's own
-outputs (tests/golden/golden_linalg.npz) and against the oracle at larger sizes."""
+outputs (tests/golden/golden_linalg.part*.npz) and against the oracle at larger sizes."""
 import numpy as np
 import pytest
 

@@ -529,3 +529,38 @@ def test_mera_sliced_layer_on_gpu(hip, placement):
   h16 = wl.mera_sliced_run(hip, chi, placement, ta.bfloat16)
   a16 = wl.mera_sliced_run(hip, chi, placement, ta.bfloat16, reuse_partials=False)
   assert h16["energy_partial_sum"] == a16["energy_partial_sum"]
+
+
+def test_bench_plain_run_dumps_the_slabs_of_its_last_step_on_gpu(hip, monkeypatch, capsys, tmp_path):
+  """`bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR` (no --full) in this process at D = 64, the smallest
+  bond whose result (64^4 float32 = 64 MiB) goes out as slabs: the line carries the contract keys and no secondary leg,
+  and every dumped [i0, i1, :, :] slab agrees with the float64 contraction of the device operands (bf16 result:
+  2^-8 |ref| + 2^-10 rms(ref), the tolerance of cases.verify_pair)."""
+  import json
+  import sys
+  import bench
+  kept = {}
+  make_nodes = bench.make_nodes
+
+  def keeping_nodes(*a, **kw):
+    kept["nodes"] = make_nodes(*a, **kw)
+    return kept["nodes"]
+
+  monkeypatch.setattr(bench, "make_nodes", keeping_nodes)
+  monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+  monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--bond", "64", "--steps", "3", "--warmup", "1",
+                                    "--dump-outputs", str(tmp_path / "dump")])
+  for var in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+    monkeypatch.delenv(var, raising=False)
+  bench.main()
+  head = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+  assert head["steps"] == 3 and head["warmup"] == 1 and head["roofline"]["launches"] == 3
+  assert head["value"] == pytest.approx(2.0 * 4096**3 / (head["ms_per_step"] * 1e-3) / 1e12, rel=1e-4)
+  assert not {"verified", "cpu_baseline", "sliced_network", "bond_sweep", "mera", "mera_chi64", "svd"} & set(head)
+  got = np.load(tmp_path / "dump" / "contract_between.npy")
+  slabs = bench.dump_slabs((64,) * 4)
+  assert got.dtype == np.float32 and got.shape == (len(slabs), 64, 64) and got.nbytes == bench.DUMP_FULL_BYTES
+  A, B = (bench.host64(t) for t in kept["nodes"])
+  ref = np.stack([A[i, j].reshape(-1) for i, j in slabs]) @ B.reshape(4096, 4096)
+  tol = 2.0**-8 * np.abs(ref) + 2.0**-10 * np.sqrt(np.mean(ref**2))
+  assert np.all(np.abs(got.reshape(ref.shape) - ref) <= tol)

@@ -344,7 +344,7 @@ def test_bench_main_assembles_its_json_line_on_the_emulated_backend(monkeypatch,
   import bench  # pylint: disable=import-outside-toplevel
   with emulated_backend() as be:
     monkeypatch.setattr(ta, "get_hip_backend", lambda: be)
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--bond", "16", "--steps", "2", "--warmup", "1", "--svd-n", "0",
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--bond", "16", "--steps", "2", "--warmup", "1", "--svd-n", "0",
                                       "--rr-bond", "3", "--rr-bond-small", "2", "--rr-min-slices", "4", "--mera-chi", "4", "--no-sweep",
                                       "--no-extras", "--no-cpu-baseline"])
     for var in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
@@ -369,6 +369,92 @@ def test_bench_main_assembles_its_json_line_on_the_emulated_backend(monkeypatch,
   assert rec["verified"]["headline_D16_L0"]["ok"] is True and rec["verified"]["mera_chi4_bf16_vs_f32"]["ok"] is True
   assert "sliced_network_bf16_vs_f32" in rec["verified"] and "all_ok" in rec["verified"]   # (the statistical model
   # behind the sliced check needs more than the 4 partials of a D = 2 toy network to hold: only its presence is asserted)
+
+
+def _plain_bench_run(monkeypatch, capsys, root, dump_dir, steps=3, warmup=2):
+  """bench.main() without --full on the emulated backend: (the parsed line, the detail record, the operands, the number
+  of contraction steps it ran)."""
+  import json  # pylint: disable=import-outside-toplevel
+  import sys  # pylint: disable=import-outside-toplevel
+  import bench  # pylint: disable=import-outside-toplevel
+  seen = {"steps": 0}
+  make_nodes, one_step = bench.make_nodes, bench.one_step
+
+  def counting_step(*a, **kw):
+    seen["steps"] += 1
+    return one_step(*a, **kw)
+
+  def keeping_nodes(*a, **kw):
+    nodes = make_nodes(*a, **kw)
+    seen["operands"] = [bench.host64(t) for t in nodes]
+    return nodes
+
+  with emulated_backend() as be:
+    monkeypatch.setattr(ta, "get_hip_backend", lambda: be)
+    monkeypatch.setattr(bench, "one_step", counting_step)
+    monkeypatch.setattr(bench, "make_nodes", keeping_nodes)
+    monkeypatch.setattr(bench, "ROOT", str(root))
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--bond", "16", "--steps", str(steps), "--warmup", str(warmup),
+                                      "--dump-outputs", str(dump_dir)])
+    for var in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+      monkeypatch.delenv(var, raising=False)
+    bench.main()
+  out = capsys.readouterr().out.strip().splitlines()
+  assert len(out) == 1
+  head = json.loads(out[0])
+  return head, json.loads((root / head["detail"]).read_text()), seen["operands"], seen["steps"]
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_what_its_last_step_returned(monkeypatch, capsys, tmp_path):
+  """`bench.py --gpus 1 --steps K --warmup W` without --full: W warm-up and exactly K timed contraction steps and not
+  one more (no value check, no secondary leg, no CPU baseline -- those are --full's), the contract keys with
+  ms_per_step = the timed region / K on the line.  `--dump-outputs DIR` writes the tensor the last timed step returned,
+  float32, here small enough to go whole: checked against the float64 contraction of the device operands (bf16 result:
+  2^-8 |ref| + 2^-10 rms(ref), the tolerance of cases.verify_pair).  A second run with the same arguments has the same
+  operands and writes the same array."""
+  head, rec, (A, B), steps = _plain_bench_run(monkeypatch, capsys, tmp_path / "a", tmp_path / "a" / "dump", steps=3, warmup=2)
+  assert steps == 3 + 2
+  for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "detail"):
+    assert key in head, key
+  assert head["steps"] == 3 and head["warmup"] == 2 and head["dtype"] == "bf16" and head["unit"] == "TFLOP/s"
+  assert head["higher_is_better"] is True and head["roofline"]["launches"] == 3       # one GEMM per timed step
+  assert head["value"] == pytest.approx(2.0 * 256**3 / (head["ms_per_step"] * 1e-3) / 1e12, rel=1e-4)
+  for leg in ("verified", "cpu_baseline", "sliced_network", "sliced_network_small", "bond_sweep", "dtype_sweep", "mera",
+              "mera_chi64", "mps_chain", "helpers", "gather_gemm", "svd"):
+    assert leg not in rec and leg not in head, leg
+  files = sorted(p.name for p in (tmp_path / "a" / "dump").iterdir())
+  assert files == ["contract_between.npy"]
+  got = np.load(tmp_path / "a" / "dump" / "contract_between.npy")
+  assert got.dtype == np.float32 and got.shape == (16,) * 4
+  ref = np.tensordot(A, B, [[2, 3], [0, 1]])
+  assert np.all(np.abs(got - ref) <= 2.0**-8 * np.abs(ref) + 2.0**-10 * np.sqrt(np.mean(ref**2)))
+  _, _, (A2, B2), _ = _plain_bench_run(monkeypatch, capsys, tmp_path / "b", tmp_path / "b" / "dump", steps=1, warmup=0)
+  assert np.array_equal(A, A2) and np.array_equal(B, B2)
+  assert np.array_equal(got, np.load(tmp_path / "b" / "dump" / "contract_between.npy"))
+
+
+def test_bench_dump_of_a_large_result_is_a_fixed_sample_of_its_slabs(tmp_path, monkeypatch):
+  """A result above DUMP_FULL_BYTES goes out as [i0, i1, :, :] slabs chosen from the shape alone: the headline's own
+  (256,)*4 gives 128 distinct slabs = 32 MiB of float32 (the limit for a dump is 64 MB), first and last included, the
+  same list on every call; and `dump_outputs` reads exactly those slabs (here with the threshold lowered to 8 slabs of
+  a (16,)*4 result)."""
+  import bench  # pylint: disable=import-outside-toplevel
+  slabs = bench.dump_slabs((256,) * 4)
+  assert len(slabs) == len(set(slabs)) == 128 and 4 * 256 * 256 * len(slabs) == bench.DUMP_FULL_BYTES <= 64e6
+  assert slabs[0] == (0, 0) and slabs[-1] == (255, 255) and slabs == sorted(slabs) == bench.dump_slabs((256,) * 4)
+  assert all(0 <= i < 256 and 0 <= j < 256 for i, j in slabs)
+  rng = np.random.default_rng(5)
+  host = orc.round_bf16(rng.standard_normal((16,) * 4).astype(np.float32))
+  monkeypatch.setattr(bench, "DUMP_FULL_BYTES", 8 * 4 * 16 * 16)
+  with emulated_backend() as be:
+    node = ta.Node(be.to_bfloat16(host), backend=be)
+    path = bench.dump_outputs(be, node, str(tmp_path / "d"), rank=1)
+  assert path.endswith("contract_between_rank1.npy")
+  got = np.load(path)
+  picks = bench.dump_slabs((16,) * 4)
+  assert got.dtype == np.float32 and got.shape == (8, 16, 16) and len(picks) == 8
+  np.testing.assert_array_equal(got, np.stack([host[i, j] for i, j in picks]))
 
 
 def test_bench_compact_line_of_a_full_size_record_stays_under_the_parser_limit():

@@ -1,6 +1,6 @@
 """CPU suite for the decomposition / dense-linalg rows: pins the oracle's
 qr / rq / eigh / inv / expm restatements against outputs of the reference itself
-(tests/golden/golden_linalg.npz) and drives the host layer's split_node_qr / split_node_rq with
+(tests/golden/golden_linalg.part*.npz) and drives the host layer's split_node_qr / split_node_rq with
 the oracle backend through the same checks the GPU suite applies to HipBackend."""
 import numpy as np
 import pytest

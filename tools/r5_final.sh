@@ -16,7 +16,7 @@ python tools/traffic_json.py $OUT $OUT/bench_detail.json $O/traffic.json > /dev/
 cat $O/traffic.json | head -20
 rm -f $OUT/prof_stats/*kernel_trace.csv $OUT/prof_stats/*/*kernel_trace.csv
 timeout 1500 python -m pytest tests -m gpu -q --timeout 900 > $O/pytest_gpu.txt 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest_gpu.txt
-timeout 1800 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.out 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err
+timeout 1800 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.out 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err
 cp $OUT/bench_detail.json $O/bench_detail.json; tail -c 4000 $O/bench.out; echo
 if [ -n "${TN_REFERENCE_DIR:-}" ]; then
   OUT=$O/refdropin PER_FILE_TIMEOUT=600 bash tools/reference_dropin/run_reference_tests.sh > $O/refdropin.log 2>&1; echo "refdropin rc=$?"; tail -14 $O/refdropin.log

@@ -5,7 +5,7 @@
 set -u
 OUT=$PWD/gpurun_out; mkdir -p $OUT
 export TNH_BENCH_FORCE_DIST=1 TNHIP_DEVICE=0 TNH_COMM_INIT_TIMEOUT_S=60
-ARGS="--gpus 2 --steps 2 --warmup 1 --bond 128 --no-sweep --no-extras --svd-n 0 --mera-chi 0 --no-cpu-baseline --rr-bond 12"
+ARGS="--full --gpus 2 --steps 2 --warmup 1 --bond 128 --no-sweep --no-extras --svd-n 0 --mera-chi 0 --no-cpu-baseline --rr-bond 12"
 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py $ARGS > $OUT/two_ranks_strict.out 2> $OUT/two_ranks_strict.err; echo "strict rc=$?"
 grep -h "did not come up" $OUT/two_ranks_strict.err | head -2 | cut -c1-300
 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29631 bench.py $ARGS --allow-host-exchange > $OUT/two_ranks_host.out 2> $OUT/two_ranks_host.err; echo "host-exchange rc=$?"
