@@ -195,6 +195,8 @@ int tnh_gemm_view(int in_dtype, int out_dtype, int64_t M, int64_t N, int64_t K, 
  * Strides other than digit 0's are multiples of 4 elements, L is 8-byte aligned, S and C 16-byte; K % 8 == 0,
  * 8 <= K <= 192, Ms <= 192 (Ms % 8 == 0 when small_first == 0), ldc % 8 == 0.  l_elems = elements of the long
  * tensor (bounds check).
+ * Wide form (192 < Ms <= 256, kernel names bf16_gather_wide_*): one box of 8 <= K <= 256 indices, no K loop
+ * (kl_ext == 1); the other rules hold as above except that Ms * ldc (small_first) and BN * ldc may be 2^30 and more.
  * K loop (kl_ext > 1): K = kl_ext * Kbox; the box holds the Kbox = K / kl_ext innermost contracted indices (the rules
  * above apply to Kbox) and the outermost contracted digit is walked step by step, kl_stride elements per step, the
  * accumulators staying in registers: a product like 144 x 248 832 x 1728 reads its long operand in place, once.

@@ -1,0 +1,108 @@
+// Pieces shared by the gather GEMM kernels (tnh_gemm_gather.hip: small operands of up to 192 rows;
+// tnh_gemm_gather_wide.hip: 193 ... 256 rows): the descriptor arithmetic and the argument block.
+#pragma once
+#include "tnh_gemm_nt.h"
+
+namespace tnh {
+
+// ---- descriptor arithmetic shared by the kernels, the host-side validation and tnh_gemm_gather_plan
+// Chunk e of a box (8 bytes: four elements of the innermost digit), e counted in memory order: e written in the
+// mixed radix of the box digits gives the digit indices, hence the element offset in the box and the image position.
+// A thread owns chunks tid, tid + 256, tid + 512, ...: tid is decoded with one division per digit, the step of
+// 256 is added digit by digit with carries afterwards (the divisions of a direct decode of every chunk were ~10 us
+// of prologue per launch: profiles/r04_gather_gemm.md).  Chunks past the end of the box repeat the last one.
+template <int NB>
+__host__ __device__ __forceinline__ void gather_thread_chunks(const tnh_gather_desc& g, int tid, int total,
+                                                              int (&off)[NB], int (&row)[NB], int (&kcol)[NB]) {
+  unsigned radix[TNH_GATHER_MAX_DIGITS], digit[TNH_GATHER_MAX_DIGITS], step[TNH_GATHER_MAX_DIGITS];
+  {
+    unsigned e = (unsigned)tid, inc = 256u;
+#pragma unroll
+    for (int d = 0; d < TNH_GATHER_MAX_DIGITS; ++d) {
+      // digits the box does not have count modulo 1 (always 0, carries fall through); the top digit is unbounded
+      radix[d] = 1u;
+      digit[d] = 0u;
+      step[d] = 0u;
+      if (d < g.nd) {
+        const unsigned ext = d == 0 ? (unsigned)g.ext[0] >> 2 : (unsigned)g.ext[d];
+        radix[d] = ext;
+        const unsigned qe = e / ext, qi = inc / ext;
+        digit[d] = e - qe * ext;
+        step[d] = inc - qi * ext;
+        e = qe;
+        inc = qi;
+      }
+    }
+  }
+  int last_off = 0, last_row = 0, last_k = 0;     // chunk total - 1: every digit at its maximum
+#pragma unroll
+  for (int d = 0; d < TNH_GATHER_MAX_DIGITS; ++d) {
+    if (d < g.nd) {
+      const int top = d == 0 ? g.ext[0] - 4 : g.ext[d] - 1;
+      last_off += top * g.stride[d];
+      if ((g.k_mask >> d) & 1) last_k += top * g.mult[d];
+      else last_row += top * g.mult[d];
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < NB; ++it) {
+    if (it * 256 + tid >= total) {
+      off[it] = last_off;
+      row[it] = last_row;
+      kcol[it] = last_k;
+    } else {
+      int o = 0, r = 0, k = 0;
+#pragma unroll
+      for (int d = 0; d < TNH_GATHER_MAX_DIGITS; ++d) {
+        if (d < g.nd) {
+          const int idx = d == 0 ? (int)(digit[0] << 2) : (int)digit[d];
+          o += idx * g.stride[d];
+          if ((g.k_mask >> d) & 1) k += idx * g.mult[d];
+          else r += idx * g.mult[d];
+        }
+      }
+      off[it] = o;
+      row[it] = r;
+      kcol[it] = k;
+    }
+    unsigned carry = 0;                            // next chunk of this thread: + 256 in the mixed radix
+#pragma unroll
+    for (int d = 0; d < TNH_GATHER_MAX_DIGITS; ++d) {
+      unsigned v = digit[d] + step[d] + carry;
+      carry = v >= radix[d] ? 1u : 0u;
+      if (carry) v -= radix[d];
+      digit[d] = v;
+    }
+  }
+}
+
+__host__ __device__ __forceinline__ int64_t gather_tile_base(const tnh_gather_desc& g, int tile) {
+  int64_t base = 0;
+  unsigned t = (unsigned)tile;
+#pragma unroll
+  for (int d = 0; d < TNH_GATHER_MAX_TILE_DIGITS; ++d) {
+    if (d < g.nt) {
+      const unsigned ext = (unsigned)g.text[d];
+      const unsigned q = t / ext;
+      base += (int64_t)(t - q * ext) * g.tstride[d];
+      t = q;
+    }
+  }
+  return base;
+}
+
+struct GatherArgs {
+  tnh_gather_desc g;
+  const uint16_t* S;   // small operand, [Ms][K] rows lds apart
+  const uint16_t* L;   // the long tensor as it lies
+  uint16_t* C;
+  int64_t lds, ldc;
+  int Ms, K;
+  int ntiles;
+};
+
+// provided by tnh_gemm_gather_wide.hip: 192 < Ms <= 256, one box of BN x K (K <= 256), descriptor already validated.
+// TNH_ERR_UNSUPPORTED, nothing launched, when the images do not fit the 160 KB of a CU.
+int launch_gather_wide(int bn, bool swap, bool kin, bool is_bf16, const GatherArgs& p, const char** name);
+
+}  // namespace tnh

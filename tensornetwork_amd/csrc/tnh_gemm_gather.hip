@@ -26,96 +26,13 @@
 // permute + tnh_gemm.
 //
 // Roofline: HBM.  Algorithmic bytes 2 * (Nl * K + Ms * K + Ms * Nl).
-#include "tnh_gemm_nt.h"
+//
+// Small operands of 193 ... 256 rows (bond D = 16) go to the kernel of tnh_gemm_gather_wide.hip; the descriptor
+// arithmetic both share is in tnh_gemm_gather.h.
+#include "tnh_gemm_gather.h"
 #include <mutex>
 
 namespace tnh {
-
-// ---- descriptor arithmetic shared by the kernel, the host-side validation and tnh_gemm_gather_plan
-// Chunk e of a box (8 bytes: four elements of the innermost digit), e counted in memory order: e written in the
-// mixed radix of the box digits gives the digit indices, hence the element offset in the box and the image position.
-// A thread owns chunks tid, tid + 256, tid + 512, ...: tid is decoded with one division per digit, the step of
-// 256 is added digit by digit with carries afterwards (the divisions of a direct decode of every chunk were ~10 us
-// of prologue per launch: profiles/r04_gather_gemm.md).  Chunks past the end of the box repeat the last one.
-template <int NB>
-__host__ __device__ __forceinline__ void gather_thread_chunks(const tnh_gather_desc& g, int tid, int total,
-                                                              int (&off)[NB], int (&row)[NB], int (&kcol)[NB]) {
-  unsigned radix[TNH_GATHER_MAX_DIGITS], digit[TNH_GATHER_MAX_DIGITS], step[TNH_GATHER_MAX_DIGITS];
-  {
-    unsigned e = (unsigned)tid, inc = 256u;
-#pragma unroll
-    for (int d = 0; d < TNH_GATHER_MAX_DIGITS; ++d) {
-      // digits the box does not have count modulo 1 (always 0, carries fall through); the top digit is unbounded
-      radix[d] = 1u;
-      digit[d] = 0u;
-      step[d] = 0u;
-      if (d < g.nd) {
-        const unsigned ext = d == 0 ? (unsigned)g.ext[0] >> 2 : (unsigned)g.ext[d];
-        radix[d] = ext;
-        const unsigned qe = e / ext, qi = inc / ext;
-        digit[d] = e - qe * ext;
-        step[d] = inc - qi * ext;
-        e = qe;
-        inc = qi;
-      }
-    }
-  }
-  int last_off = 0, last_row = 0, last_k = 0;     // chunk total - 1: every digit at its maximum
-#pragma unroll
-  for (int d = 0; d < TNH_GATHER_MAX_DIGITS; ++d) {
-    if (d < g.nd) {
-      const int top = d == 0 ? g.ext[0] - 4 : g.ext[d] - 1;
-      last_off += top * g.stride[d];
-      if ((g.k_mask >> d) & 1) last_k += top * g.mult[d];
-      else last_row += top * g.mult[d];
-    }
-  }
-#pragma unroll
-  for (int it = 0; it < NB; ++it) {
-    if (it * 256 + tid >= total) {
-      off[it] = last_off;
-      row[it] = last_row;
-      kcol[it] = last_k;
-    } else {
-      int o = 0, r = 0, k = 0;
-#pragma unroll
-      for (int d = 0; d < TNH_GATHER_MAX_DIGITS; ++d) {
-        if (d < g.nd) {
-          const int idx = d == 0 ? (int)(digit[0] << 2) : (int)digit[d];
-          o += idx * g.stride[d];
-          if ((g.k_mask >> d) & 1) k += idx * g.mult[d];
-          else r += idx * g.mult[d];
-        }
-      }
-      off[it] = o;
-      row[it] = r;
-      kcol[it] = k;
-    }
-    unsigned carry = 0;                            // next chunk of this thread: + 256 in the mixed radix
-#pragma unroll
-    for (int d = 0; d < TNH_GATHER_MAX_DIGITS; ++d) {
-      unsigned v = digit[d] + step[d] + carry;
-      carry = v >= radix[d] ? 1u : 0u;
-      if (carry) v -= radix[d];
-      digit[d] = v;
-    }
-  }
-}
-
-__host__ __device__ __forceinline__ int64_t gather_tile_base(const tnh_gather_desc& g, int tile) {
-  int64_t base = 0;
-  unsigned t = (unsigned)tile;
-#pragma unroll
-  for (int d = 0; d < TNH_GATHER_MAX_TILE_DIGITS; ++d) {
-    if (d < g.nt) {
-      const unsigned ext = (unsigned)g.text[d];
-      const unsigned q = t / ext;
-      base += (int64_t)(t - q * ext) * g.tstride[d];
-      t = q;
-    }
-  }
-  return base;
-}
 
 // Zero, but not to the optimiser: added to an address computation inside a loop body it keeps that computation IN the
 // body (hoisted out, the per-thread addresses of the K-loop kernel's small slice and epilogue cost ~50 registers and
@@ -125,16 +42,6 @@ __device__ __forceinline__ int opaque_zero() {
   asm volatile("" : "+s"(z));
   return z;
 }
-
-struct GatherArgs {
-  tnh_gather_desc g;
-  const uint16_t* S;   // small operand, [Ms][K] rows lds apart
-  const uint16_t* L;   // the long tensor as it lies
-  uint16_t* C;
-  int64_t lds, ldc;
-  int Ms, K;
-  int ntiles;
-};
 
 // LDS as in tnh_gemm_stream.hip: [ small image: msf*16 rows x PA ][ R: max(long image BN x PA, staging) ].
 // KIN: the innermost digit of the box is contracted (8-byte image stores); otherwise it is free (2-byte stores).
@@ -538,8 +445,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 // ---- host side
-// Everything the kernel relies on, checked by brute force over the <= 3072 chunks of a box (rows and columns of the
-// image are hit exactly once, offsets stay inside the tensor).  Returns the tile height BN (48 / 64) or 0.
+// Everything the kernels rely on, checked by brute force over the <= 4096 chunks of a box (rows and columns of the
+// image are hit exactly once, offsets stay inside the tensor).  Returns the tile height BN (48 / 64) or 0.  Boxes of
+// up to 64 x 256 pass (the wide kernel's range); gemm_gather keeps the narrow kernels to K <= 192.
 static int gather_validate(const tnh_gather_desc& g, int64_t K, int64_t Nl, int64_t l_elems, const char** why) {
   *why = nullptr;
   if (g.nd < 1 || g.nd > TNH_GATHER_MAX_DIGITS || g.nt < 0 || g.nt > TNH_GATHER_MAX_TILE_DIGITS) {
@@ -556,7 +464,7 @@ static int gather_validate(const tnh_gather_desc& g, int64_t K, int64_t Nl, int6
     if ((g.k_mask >> d) & 1) cols *= g.ext[d];
     else rows *= g.ext[d];
     span += (int64_t)(g.ext[d] - 1) * g.stride[d];
-    if (rows > 64 || cols > 192 || span >= (int64_t(1) << 31)) { *why = "box too large"; return 0; }
+    if (rows > 64 || cols > 256 || span >= (int64_t(1) << 31)) { *why = "box too large"; return 0; }
   }
   if (cols != K || (rows != 48 && rows != 64)) { *why = "box is not BN x K with BN = 48 or 64"; return 0; }
   int64_t tiles = 1, tspan = 0;
@@ -575,18 +483,18 @@ static int gather_validate(const tnh_gather_desc& g, int64_t K, int64_t Nl, int6
   // the image is covered exactly once
   const int total = (int)(rows * (K >> 2));
   const bool kin = g.k_mask & 1;
-  unsigned char seen[64 * 48];
+  unsigned char seen[64 * 64];
   memset(seen, 0, sizeof(seen));
   for (int tid = 0; tid < 256; ++tid) {
-    int coff[12], crow[12], ccol[12];
-    gather_thread_chunks<12>(g, tid, total, coff, crow, ccol);      // the kernel's own decode, thread by thread
-    for (int it = 0; it < 12 && it * 256 + tid < total; ++it) {
+    int coff[16], crow[16], ccol[16];
+    gather_thread_chunks<16>(g, tid, total, coff, crow, ccol);      // the kernel's own decode, thread by thread
+    for (int it = 0; it < 16 && it * 256 + tid < total; ++it) {
       const int off = coff[it], row = crow[it], kcol = ccol[it];
       if (off < 0 || off > span || row < 0 || kcol < 0) { *why = "chunk out of the box"; return 0; }
       for (int i = 0; i < 4; ++i) {
         const int r = kin ? row : row + i, c = kin ? kcol + i : kcol;
         if (r >= rows || c >= K) { *why = "chunk leaves the image"; return 0; }
-        unsigned char& cell = seen[r * 48 + (c >> 2)];
+        unsigned char& cell = seen[r * 64 + (c >> 2)];
         const unsigned char bit = (unsigned char)(1u << (c & 3));
         if (cell & bit) { *why = "two chunks write one image element"; return 0; }
         cell |= bit;
@@ -681,13 +589,17 @@ int gemm_gather(int dtype, int64_t Ms, int64_t K, int64_t Nl, const void* S, int
   int bn = 0;
   const int64_t steps = desc->kl_ext >= 1 ? desc->kl_ext : 0;       // K = steps * Kbox (steps == 1: no K loop)
   const int64_t Kbox = steps && K % steps == 0 ? K / steps : 0;
-  const bool shape_ok = gather_enabled() && Ms >= 1 && Ms <= 192 && Kbox >= 8 && Kbox <= 192 && Kbox % 8 == 0 && Nl >= 48 &&
+  // 192 < Ms <= 256: the wide kernel (tnh_gemm_gather_wide.hip) -- one box of up to 256 contracted indices, no K loop
+  const bool wide = Ms > 192;
+  const bool range_ok = wide ? Ms <= 256 && Kbox <= 256 && steps == 1
+                             : Ms >= 1 && Kbox <= 192 && (steps == 1 || Ms * (Kbox / 8) <= 11 * 256);
+  const bool shape_ok = gather_enabled() && range_ok && Kbox >= 8 && Kbox % 8 == 0 && Nl >= 48 &&
                         lds % 8 == 0 && ldc % 8 == 0 && lds >= K && ((uintptr_t)S % 16) == 0 &&
                         ((uintptr_t)L % 8) == 0 && ((uintptr_t)C % 16) == 0 && (!swap || Ms % 8 == 0) &&
-                        ldc >= (swap ? Ms : Nl) && Ms * lds < (int64_t(1) << 30) &&
-                        (steps == 1 || Ms * (Kbox / 8) <= 11 * 256);
+                        ldc >= (swap ? Ms : Nl) && Ms * lds < (int64_t(1) << 30);
   if (shape_ok) bn = gather_validate_cached(*desc, Kbox, Nl, l_elems, &why);
-  if (shape_ok && bn && (swap ? (int64_t)bn * ldc : Ms * ldc) >= (int64_t(1) << 30)) {
+  // (the wide kernel addresses C with a 64-bit row base: no such rule)
+  if (shape_ok && bn && !wide && (swap ? (int64_t)bn * ldc : Ms * ldc) >= (int64_t(1) << 30)) {
     bn = 0;
     why = "32-bit offsets inside one output tile";
   }
@@ -706,6 +618,7 @@ int gemm_gather(int dtype, int64_t Ms, int64_t K, int64_t Nl, const void* S, int
   p.Ms = (int)Ms;
   p.K = (int)Kbox;
   p.ntiles = (int)(Nl / bn);
+  if (wide) return launch_gather_wide(bn, swap, desc->k_mask & 1, dtype == TNH_BF16, p, name);
   const int Kp = (int)((Kbox + 31) & ~31), PA = Kp * 2 + 16;
   const int msp = (p.Ms + 15) / 16 * 16;
   const size_t image = (size_t)bn * PA;
@@ -737,9 +650,9 @@ int gemm_gather_plan(const tnh_gather_desc* desc, int64_t K, int64_t Nl, int64_t
   TNH_REQUIRE(nchunks >= 0 && nchunks <= total && ntiles >= 0 && ntiles <= Nl / bn,
               "tnh_gemm_gather_plan: more chunks / tiles asked than there are");
   for (int tid = 0; tid < 256; ++tid) {
-    int coff[12], crow[12], ccol[12];
-    gather_thread_chunks<12>(*desc, tid, (int)total, coff, crow, ccol);
-    for (int it = 0; it < 12; ++it) {
+    int coff[16], crow[16], ccol[16];
+    gather_thread_chunks<16>(*desc, tid, (int)total, coff, crow, ccol);
+    for (int it = 0; it < 16; ++it) {
       const int64_t e = (int64_t)it * 256 + tid;
       if (e >= nchunks) break;
       chunk_off[e] = coff[it];

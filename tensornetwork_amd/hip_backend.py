@@ -204,8 +204,15 @@ def _gather_descriptor_cached(shape, k_axes, max_box_k):
     return None
   if split == 0 and t_split % 4:
     return None
-  if sum((d[0] - 1) * d[1] for d in digits) >= 1 << 31 or kl_ext > 4096 or (kl_ext > 1 and kl_stride % 4):
-    return None                                 # (the descriptor holds 32-bit box offsets)
+  # (the descriptor holds 32-bit offsets inside a box and 64-bit box origins.  Descriptors for the narrow kernels keep
+  #  their older rule, the whole tensor below 2^31 elements; the wide kernel's -- bond D = 16 is 2^32 elements -- bound
+  #  the box alone, as tnh_gemm_gather itself does)
+  if max_box_k <= 192:
+    span = sum((d[0] - 1) * d[1] for d in digits)
+  else:
+    span = sum(((t_split if i == split else d[0]) - 1) * d[1] for i, d in enumerate(digits) if d[2] or i <= split)
+  if span >= 1 << 31 or kl_ext > 4096 or (kl_ext > 1 and kl_stride % 4):
+    return None
   desc = _lib.GatherDesc()
   nd, w_row, w_k = 0, 1, 1
   for i, (ext, stride, is_k) in enumerate(digits):
@@ -368,6 +375,10 @@ class HipBackend(BackendBase):
     self.gather_gemm = os.environ.get("TNH_GATHER_GEMM", "1") != "0"
     self.gather_min_rows = 1 << 16
     self.gather_min_piece_bytes = int(os.environ.get("TNH_GATHER_MIN_PIECE", "256"))
+    # Small operands of 193 ... `gather_max_small` free tuples (bond D = 16: 256) against ONE box of up to 256
+    # contracted indices go to the wide kernel (tnh_gemm_gather_wide.hip), but only where the lowerings below would
+    # K1-permute the long operand (TNH_GATHER_WIDE=0: 192, the wide kernel is never asked).
+    self.gather_max_small = 192 if os.environ.get("TNH_GATHER_WIDE", "1") == "0" else 256
     self.gather_launches = 0     # tnh_gemm_gather launches
     self.permutes_absorbed = 0   # tnh_gemm_view launches
     self.permute_launches = 0    # K1 launches (transpose)
@@ -769,7 +780,7 @@ class HipBackend(BackendBase):
       try:
         key = (a._shape, b._shape, tuple(axes[0]), tuple(axes[1]), a._code,     # pylint: disable=protected-access
                None if hint_a is None else tuple(hint_a), None if hint_b is None else tuple(hint_b), allow_swap,
-               self.gather_gemm, self.absorb_transposes, self.half_output)
+               self.gather_gemm, self.absorb_transposes, self.half_output, self.gather_max_small)
         plan = self._td_plans.get(key)
       except TypeError:      # (an integer `axes`, unhashable entries: the general walk below)
         key = plan = None
@@ -798,21 +809,41 @@ class HipBackend(BackendBase):
     if code in _HALF:       # products the gather / in-place lowerings may take (by shape alone) are not planned
       ms, nl = (m, n) if m <= n else (n, m)
       if (64 < ms <= 192 and 16 <= k <= 192 * 4096 and k % 8 == 0 and nl >= self.gather_min_rows) or \
+          (192 < ms <= self.gather_max_small and 8 <= k <= 256 and k % 8 == 0 and nl >= self.gather_min_rows) or \
           not (m < 256 or n < 256 or ((m + 255) // 256) * ((n + 255) // 256) < 192 or k % 64 or k < 128):
         key = None
+
+    def gathered(got):
+      out, used_a, used_b, swapped = got
+      shape_a, shape_b = tuple(a.shape[i] for i in used_a), tuple(b.shape[i] for i in used_b)
+      return out.view(shape_b + shape_a if swapped else shape_a + shape_b), used_a, used_b, swapped
+
+    wide = None       # the wide gather kernel's attempt: made where a lowering below is about to permute the long operand
     if code in _HALF and self.gather_gemm and self.half_output == "same":
       got = self._tensordot_gather(a, b, axes_a, axes_b, free_a, free_b, m, n, k, hint_a, hint_b, allow_swap)
       if got is not None:
-        out, used_a, used_b, swapped = got
-        shape_a, shape_b = tuple(a.shape[i] for i in used_a), tuple(b.shape[i] for i in used_b)
-        return out.view(shape_b + shape_a if swapped else shape_a + shape_b), used_a, used_b, swapped
+        return gathered(got)
+      if 192 < min(m, n) <= self.gather_max_small:
+        tried = []
+
+        def wide():
+          if not tried:
+            tried.append(self._tensordot_gather(a, b, axes_a, axes_b, free_a, free_b, m, n, k, hint_a, hint_b,
+                                                allow_swap, wide=True))
+          return tried[0]
     if code in _HALF and self.absorb_transposes:
       a_shape0, b_shape0 = a.shape, b.shape
-      got = self._tensordot_in_place(a, b, axes_a, axes_b, free_a, free_b, m, n, k, hint_a, hint_b)
+      got = self._tensordot_in_place(a, b, axes_a, axes_b, free_a, free_b, m, n, k, hint_a, hint_b, wide)
+      if got is not None and len(got) == 4:
+        return gathered(got)
       if got is not None:
         out, used_a, used_b = got
         out_shape = tuple(a_shape0[i] for i in used_a) + tuple(b_shape0[i] for i in used_b)
         return out.view(out_shape), used_a, used_b, False
+    if wide is not None:      # (the permute + ONE GEMM lowering below permutes a long operand whose contracted axes are not trailing)
+      got = wide()
+      if got is not None:
+        return gathered(got)
     a, b = self._dense(a), self._dense(b)
     plan = self._plan_generic(a.shape, b.shape, axes_a, axes_b, free_a, free_b, m, n, k, code, hint_a, hint_b)
     if key is not None and alias is None:
@@ -950,9 +981,11 @@ class HipBackend(BackendBase):
     return out, list(plan.free_a), list(plan.free_b), False
 
   def _tensordot_gather(self, a, b, axes_a, axes_b, free_a, free_b, m, n, k, hint_a=None, hint_b=None,
-                        allow_swap=False):
+                        allow_swap=False, wide=False):
     """One `tnh_gemm_gather` launch for a SMALL operand (65 ... 192 free tuples) against a long many-axis
-    tensor whose contracted axes are not trailing, or None (the caller's permute + GEMM lowering runs;
+    tensor whose contracted axes are not trailing; `wide`: the same for 193 ... `gather_max_small` free tuples and
+    at most 256 contracted indices in ONE box (the wide kernel; asked only where the long operand would be permuted
+    otherwise).  Or None (the caller's permute + GEMM lowering runs;
     results are bit-identical either way for K <= 192; beyond that the kernel walks the outermost contracted
     axis step by step -- same products, another grouping of the fp32 sums than the tile kernels').  The long tensor is read where it lies, so its free axes
     come out in natural order whatever the planner hinted -- the NEXT contraction gathers it again instead
@@ -963,7 +996,10 @@ class HipBackend(BackendBase):
     Returns (tensor, used_free_a, used_free_b, swapped)."""
     small_first = m <= n
     ms, nl = (m, n) if small_first else (n, m)
-    if not (64 < ms <= 192 and 16 <= k <= 192 * 4096 and k % 8 == 0 and nl >= self.gather_min_rows):
+    if wide:
+      if not (192 < ms <= self.gather_max_small and 8 <= k <= 256 and k % 8 == 0 and nl >= self.gather_min_rows):
+        return None
+    elif not (64 < ms <= 192 and 16 <= k <= 192 * 4096 and k % 8 == 0 and nl >= self.gather_min_rows):
       return None
     long_rows_first = not small_first or (allow_swap and ms % 8 == 0)     # C[Nl, Ms]: the kernel's "swap" form
     if long_rows_first and ms % 8:
@@ -977,10 +1013,12 @@ class HipBackend(BackendBase):
     nc = len(axes_l)
     if sorted(axes_l) == list(range(long_.ndim - nc, long_.ndim)):
       return None       # contracted axes trailing: the streaming kernel reads it as it is
-    plan = _gather_descriptor(long_.shape, axes_l)
+    plan = _gather_descriptor(long_.shape, axes_l, max_box_k=256) if wide else _gather_descriptor(long_.shape, axes_l)
     if plan is None:
       return None
     desc, _, rows = plan
+    if wide and desc.kl_ext != 1:
+      return None
     if desc.kl_ext > 1 and ms * (k // desc.kl_ext // 8) > 11 * 256:
       return None       # (the K-loop kernel re-stages an Ms x K / steps slice of the small operand per step)
     planned = allow_swap or hint_a is not None or hint_b is not None
@@ -1011,7 +1049,7 @@ class HipBackend(BackendBase):
       return out, used_s, used_l, long_rows_first       # (swapped: b's axes, the long operand's, come first)
     return out, used_l, used_s, False
 
-  def _tensordot_in_place(self, a, b, axes_a, axes_b, free_a, free_b, m, n, k, hint_a=None, hint_b=None):
+  def _tensordot_in_place(self, a, b, axes_a, axes_b, free_a, free_b, m, n, k, hint_a=None, hint_b=None, wide=None):
     """One `tnh_gemm_view` launch that reads the operands as they lie in HBM wherever that pays, or None
     (caller falls back to the classic permute + tnh_gemm lowering; results are bit-identical either way).
 
@@ -1020,7 +1058,9 @@ class HipBackend(BackendBase):
     in place when `_operand_view` offers a view and the size / intensity gate in `usable` below lets it.
     Operands that are not read
     in place are permuted to [free..., contracted...] (free order = the planner's hint when given) and
-    viewed trivially.  Returns (tensor, used_free_a, used_free_b)."""
+    viewed trivially.  Returns (tensor, used_free_a, used_free_b).  `wide` (the caller's attempt at the wide gather
+    kernel, or None) is called where the long operand is about to be permuted; when it delivers, its four values
+    (`_tensordot_gather`'s) are returned instead."""
     if m < 256 or n < 256 or ((m + 255) // 256) * ((n + 255) // 256) < 192 or k % 64 or k < 128:
       return None
     if a.ptr % 16 or b.ptr % 16:
@@ -1101,6 +1141,12 @@ class HipBackend(BackendBase):
       if best is None or cost < best[0]:
         best = (cost, ka, kb, va, vb)
     _, ka, kb, va, vb = best
+    if wide is not None and (vb if m <= n else va) is None:
+      # about to K1-permute the long operand: the wide gather kernel reads it where it lies instead (its result is
+      # returned as `_tensordot_gather` gives it, four values)
+      got = wide()
+      if got is not None:
+        return got
     used_a, used_b = list(free_a), list(free_b)
     if va is None:
       if hint_a is not None and sorted(hint_a) == sorted(free_a):
