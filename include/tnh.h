@@ -224,6 +224,33 @@ int tnh_gemm_gather(int dtype, int64_t Ms, int64_t K, int64_t Nl, const void* S,
  * rows otherwise) and the origins of the first `ntiles` boxes.  Returns BN (> 0) or a negative tnh_status. */
 int tnh_gemm_gather_plan(const tnh_gather_desc* desc, int64_t K, int64_t Nl, int64_t l_elems, int32_t* chunk_off,
                          int32_t* chunk_row, int32_t* chunk_k, int64_t nchunks, int64_t* tile_base, int64_t ntiles);
+/* tnh_gemm_gather with a SCATTERED EPILOGUE: the same product (one box, kl_ext == 1, Ms <= 192, 8 <= K <= 192), written
+ * into a dense destination C whose axes are any permutation of [long operand's free axes..., small operand's free
+ * axes...] -- the order the NEXT contraction wants, so no tnh_permute runs between the two.  The destination offset of
+ * an element separates into  tile part + box-row part + small-row part:
+ *   omult[d]     elements per index of box digit d of `desc` (free digits; entries of contracted digits are ignored)
+ *   otstride[d]  elements per index of tile digit d of `desc`
+ *   sext / sstride / ns   the small operand's free digits, innermost first (row c of S in their mixed radix)
+ *   c_elems      elements of C (bounds check)
+ * There is no ldc and no small_first: the descriptor says where everything goes, and offsets are 64-bit throughout.
+ * The destination's innermost axis must be the innermost free digit of the small operand or the innermost free digit of
+ * the box, and the contiguous run that starts there a multiple of 4 elements (C 8-byte aligned; 16-byte stores when
+ * the run is a multiple of 8 and C 16-byte aligned): TNH_ERR_UNSUPPORTED otherwise, nothing launched, like every other
+ * rule of tnh_gemm_gather (or TNH_GATHER_SCATTER=0).  TNH_ERR_INVALID when the described destination is not a bijection
+ * onto [0, Ms * Nl).  Results are bit-identical to tnh_gemm_gather + tnh_permute (same MFMA sequence).
+ * Kernel names: bf16_gather_scatter_{64,48}xS_v{16,8} (staged [BN][Ms], runs along the small operand's axes) and
+ * bf16_gather_scatter_Sx{64,48}_v{16,8} (staged [Ms][BN], runs along the box rows); v = bytes per store. */
+#define TNH_SCATTER_MAX_SMALL_DIGITS 8
+typedef struct {
+  int64_t omult[TNH_GATHER_MAX_DIGITS];
+  int64_t otstride[TNH_GATHER_MAX_TILE_DIGITS];
+  int64_t sstride[TNH_SCATTER_MAX_SMALL_DIGITS];
+  int32_t sext[TNH_SCATTER_MAX_SMALL_DIGITS];
+  int32_t ns;
+  int64_t c_elems;
+} tnh_scatter_desc;
+int tnh_gemm_gather_scatter(int dtype, int64_t Ms, int64_t K, int64_t Nl, const void* S, int64_t lds, const void* L,
+                            int64_t l_elems, const tnh_gather_desc* desc, void* C, const tnh_scatter_desc* out);
 const char* tnh_gemm_last_kernel(void);
 /* Force a variant ("auto", "generic", "valu", "bf16_128", "bf16_256", "bf16_256pp", "bf16_ragged*"),
  * optionally followed by A/B knobs ":r<d>" (tile order: 1 = super-tiles shared by the XCDs, 0 / 2 / 3 / 4 =

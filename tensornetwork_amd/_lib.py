@@ -44,6 +44,15 @@ class GatherDesc(ctypes.Structure):
               ("kl_ext", c_int32), ("kl_stride", c_int64)]
 
 
+SCATTER_MAX_SMALL_DIGITS = 8
+
+class ScatterDesc(ctypes.Structure):
+  """tnh_scatter_desc (include/tnh.h): where tnh_gemm_gather_scatter writes, digit by digit."""
+  _fields_ = [("omult", c_int64 * GATHER_MAX_DIGITS), ("otstride", c_int64 * GATHER_MAX_TILE_DIGITS),
+              ("sstride", c_int64 * SCATTER_MAX_SMALL_DIGITS), ("sext", c_int32 * SCATTER_MAX_SMALL_DIGITS),
+              ("ns", c_int32), ("c_elems", c_int64)]
+
+
 _I64P = POINTER(c_int64)
 _I32P = POINTER(c_int32)
 
@@ -91,6 +100,8 @@ SIGNATURES = {
                                 POINTER(GatherDesc), c_void_p, c_int64, c_int]),
     "tnh_gemm_gather_plan": (c_int, [POINTER(GatherDesc), c_int64, c_int64, c_int64, _I32P, _I32P, _I32P, c_int64,
                                      _I64P, c_int64]),
+    "tnh_gemm_gather_scatter": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                        POINTER(GatherDesc), c_void_p, POINTER(ScatterDesc)]),
     "tnh_gemm_view": (c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, POINTER(OperandView),
                               c_void_p, POINTER(OperandView), c_void_p, c_int64]),
     "tnh_complex_expand": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int]),

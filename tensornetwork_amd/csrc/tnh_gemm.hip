@@ -47,6 +47,10 @@ int gemm_gather(int dtype, int64_t Ms, int64_t K, int64_t Nl, const void* S, int
                 const char** name);
 int gemm_gather_plan(const tnh_gather_desc* desc, int64_t K, int64_t Nl, int64_t l_elems, int32_t* chunk_off,
                      int32_t* chunk_row, int32_t* chunk_k, int64_t nchunks, int64_t* tile_base, int64_t ntiles);
+// provided by tnh_gemm_gather_scatter.hip
+int gemm_gather_scatter(int dtype, int64_t Ms, int64_t K, int64_t Nl, const void* S, int64_t lds, const void* L,
+                        int64_t l_elems, const tnh_gather_desc* desc, void* C, const tnh_scatter_desc* out,
+                        const char** name);
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -1169,6 +1173,22 @@ int tnh_gemm_gather(int dtype, int64_t Ms, int64_t K, int64_t Nl, const void* S,
   }
   const char* name = nullptr;
   const int rc = gemm_gather(dtype, Ms, K, Nl, S, lds, L, l_elems, desc, C, ldc, small_first, &name);
+  if (rc == TNH_OK) g_last_kernel = name;
+  return rc;
+}
+
+int tnh_gemm_gather_scatter(int dtype, int64_t Ms, int64_t K, int64_t Nl, const void* S, int64_t lds, const void* L,
+                            int64_t l_elems, const tnh_gather_desc* desc, void* C, const tnh_scatter_desc* out) {
+  TNH_NEED_INIT();
+  TNH_REQUIRE(desc != nullptr && out != nullptr && S != nullptr && L != nullptr && C != nullptr,
+              "tnh_gemm_gather_scatter: null argument");
+  TNH_REQUIRE(dtype == TNH_BF16 || dtype == TNH_F16, "tnh_gemm_gather_scatter: bf16 / f16 only");
+  if (g_variant != 0) {   // a kernel forced through tnh_gemm_set_variant: the caller's fallback path runs it
+    set_error("tnh_gemm_gather_scatter: a GEMM variant is forced");
+    return TNH_ERR_UNSUPPORTED;
+  }
+  const char* name = nullptr;
+  const int rc = gemm_gather_scatter(dtype, Ms, K, Nl, S, lds, L, l_elems, desc, C, out, &name);
   if (rc == TNH_OK) g_last_kernel = name;
   return rc;
 }

@@ -1,5 +1,6 @@
 // Pieces shared by the gather GEMM kernels (tnh_gemm_gather.hip: small operands of up to 192 rows;
-// tnh_gemm_gather_wide.hip: 193 ... 256 rows): the descriptor arithmetic and the argument block.
+// tnh_gemm_gather_wide.hip: 193 ... 256 rows; tnh_gemm_gather_scatter.hip: up to 192 rows, result written in the
+// consumer's axis order): the descriptor arithmetic and the argument block.
 #pragma once
 #include "tnh_gemm_nt.h"
 
@@ -100,6 +101,10 @@ struct GatherArgs {
   int Ms, K;
   int ntiles;
 };
+
+// provided by tnh_gemm_gather.hip: everything the kernels rely on in a descriptor, checked on the host (the last few
+// accepted ones are remembered).  Returns the tile height BN (48 / 64), or 0 with the reason in *why.
+int gather_validate_cached(const tnh_gather_desc& g, int64_t K, int64_t Nl, int64_t l_elems, const char** why);
 
 // provided by tnh_gemm_gather_wide.hip: 192 < Ms <= 256, one box of BN x K (K <= 256), descriptor already validated.
 // TNH_ERR_UNSUPPORTED, nothing launched, when the images do not fit the 160 KB of a CU.

@@ -505,8 +505,8 @@ static int gather_validate(const tnh_gather_desc& g, int64_t K, int64_t Nl, int6
 }
 
 // The check costs ~0.1 ms of host time and a contraction path asks for the same few descriptors slice after slice:
-// the last 32 accepted (descriptor, K, Nl, elements) are remembered.
-static int gather_validate_cached(const tnh_gather_desc& g, int64_t K, int64_t Nl, int64_t l_elems, const char** why) {
+// the last 32 accepted (descriptor, K, Nl, elements) are remembered.  (Shared with tnh_gemm_gather_scatter.hip.)
+int gather_validate_cached(const tnh_gather_desc& g, int64_t K, int64_t Nl, int64_t l_elems, const char** why) {
   struct Entry {
     tnh_gather_desc g;
     int64_t K, Nl, l_elems;

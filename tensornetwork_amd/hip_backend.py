@@ -249,6 +249,67 @@ def _gather_descriptor_cached(shape, k_axes, max_box_k):
   return desc, bn, rows
 
 
+def _scatter_descriptor(shape, k_axes, out_strides, small_ext, small_strides):
+  """see _scatter_descriptor_cached"""
+  return _scatter_descriptor_cached(tuple(int(n) for n in shape), tuple(int(x) for x in k_axes),
+                                    tuple(int(s) for s in out_strides), tuple(int(n) for n in small_ext),
+                                    tuple(int(s) for s in small_strides))
+
+
+@functools.lru_cache(maxsize=512)
+def _scatter_descriptor_cached(shape, k_axes, out_strides, small_ext, small_strides):
+  """Output descriptor (tnh_scatter_desc, include/tnh.h) that goes with `_gather_descriptor(shape, k_axes)` for
+  tnh_gemm_gather_scatter: `out_strides[ax]` = elements of the destination per index of the long tensor's axis `ax`
+  (contracted axes: anything), `small_ext` / `small_strides` = the small operand's free axes in the order of its rows
+  (outermost first) with their destination strides.  Returns (gather descriptor, scatter descriptor, BN, run_elements)
+  or None: no one-box gather plan, or a digit of the plan -- memory-adjacent free axes merged into one -- whose indices
+  are not evenly spaced in the destination (those axes were pulled apart or swapped there).  `run_elements`: the
+  contiguous run of the destination the kernel's stores are made of, 0 when its innermost axis is neither the small
+  operand's innermost free axis nor the box's innermost free digit (the kernel refuses those)."""
+  plan = _gather_descriptor_cached(shape, k_axes, 192)
+  if plan is None or plan[0].kl_ext != 1 or not 1 <= len(small_ext) <= _lib.SCATTER_MAX_SMALL_DIGITS:
+    return None
+  desc, bn, rows = plan
+
+  def out_step(ext, stride):
+    """destination elements per index of a digit (extent, stride in the long tensor), None when not evenly spaced"""
+    idx = np.unravel_index(np.arange(ext, dtype=np.int64) * stride, shape)
+    off = sum(i.astype(np.int64) * s for i, s in zip(idx, out_strides) if s)
+    off = np.broadcast_to(off, (ext,))
+    step = int(off[1]) if ext > 1 else 0
+    return step if np.array_equal(off, np.arange(ext, dtype=np.int64) * step) else None
+
+  out = _lib.ScatterDesc()
+  box = []                                       # free digits of the box: (extent, destination step)
+  for d in range(desc.nd):
+    if (desc.k_mask >> d) & 1:
+      continue
+    step = out_step(desc.ext[d], desc.stride[d])
+    if step is None:
+      return None
+    out.omult[d] = step
+    box.append((desc.ext[d], step))
+  for d in range(desc.nt):
+    step = out_step(desc.text[d], desc.tstride[d])
+    if step is None:
+      return None
+    out.otstride[d] = step
+  out.ns = len(small_ext)
+  for d, (ext, stride) in enumerate(zip(reversed(small_ext), reversed(small_strides))):
+    out.sext[d], out.sstride[d] = ext, stride
+  out.c_elems = rows * _prod(small_ext)
+  run = 0
+  for side in (list(zip(reversed(small_ext), reversed(small_strides))), box):
+    side = [(e, s) for e, s in side if e != 1]
+    if side and side[0][1] == 1:
+      run = 1
+      for ext, stride in side:
+        if stride != run:
+          break
+        run *= ext
+  return desc, out, bn, run
+
+
 def _gather_piece_bytes(desc, itemsize=2):
   """bytes of the contiguous pieces of memory a box is made of (its leading digits while each starts where the
   one before ends)"""
@@ -380,6 +441,15 @@ class HipBackend(BackendBase):
     # K1-permute the long operand (TNH_GATHER_WIDE=0: 192, the wide kernel is never asked).
     self.gather_max_small = 192 if os.environ.get("TNH_GATHER_WIDE", "1") == "0" else 256
     self.gather_launches = 0     # tnh_gemm_gather launches
+    # `tensordot_planned(..., result_order=...)`: the gather GEMM writes its result straight in the axis order the
+    # caller names (tnh_gemm_gather_scatter) instead of natural order + one K1 permute (TNH_GATHER_SCATTER=0: off).
+    # `gather_scatter_min_run_bytes`: the contiguous run of the destination from which the CONTRACTORS ask for it
+    # (None: they do not).  24 bytes, the shortest run there is at D = 12, already beat gather + K1 3.6 x
+    # (profiles/gather_scatter.md).
+    self.gather_scatter = os.environ.get("TNH_GATHER_SCATTER", "1") != "0"
+    _min_run = os.environ.get("TNH_GATHER_SCATTER_MIN_RUN", "24")      # "off": the contractors never ask
+    self.gather_scatter_min_run_bytes = int(_min_run) if _min_run.isdigit() else None
+    self.gather_scatter_launches = 0     # tnh_gemm_gather_scatter launches
     self.permutes_absorbed = 0   # tnh_gemm_view launches
     self.permute_launches = 0    # K1 launches (transpose)
     self._direct_launches = type(self).transpose is HipBackend.transpose and type(self)._gemm is HipBackend._gemm
@@ -742,7 +812,7 @@ class HipBackend(BackendBase):
   def tensordot(self, a, b, axes):
     return self._tensordot_impl(a, b, axes, None, None)[0]
 
-  def tensordot_planned(self, a, b, axes, free_order_a=None, free_order_b=None, allow_swap=False):
+  def tensordot_planned(self, a, b, axes, free_order_a=None, free_order_b=None, allow_swap=False, result_order=None):
     """``tensordot`` whose result may carry the free axes of an operand in a caller-chosen order
     -- but only where that is FREE: an operand that needs a K1 permute anyway (its contracted axes
     are neither leading nor trailing) is permuted straight into ``free_order_x + contracted``;
@@ -755,9 +825,133 @@ class HipBackend(BackendBase):
     ``allow_swap=True`` (callers for whom the axis order of the result is bookkeeping) returns a fourth value
     ``swapped``: when true the result carries ``b``'s free axes FIRST, then ``a``'s -- the gather lowering writes
     [long operand's axes..., small operand's axes] whichever operand the long one is, because that output tile is
-    one contiguous block of memory."""
+    one contiguous block of memory.
+
+    ``result_order`` (a permutation of the result's axes, expressed over ``[a's free axes..., b's free axes...]`` in
+    their natural order) fixes the axis order of the result outright: the tensor comes back as
+    ``transpose(tensordot(a, b, axes), result_order)``, bit for bit.  Where the gather GEMM takes the product it
+    writes that order itself (``tnh_gemm_gather_scatter``, no K1 pass over the result); everywhere else the usual
+    lowering runs, followed by one ``transpose``.  The per-operand orders and ``allow_swap`` are not consulted then;
+    ``used_a`` / ``used_b`` are the natural free axes and ``swapped`` is false."""
+    if result_order is not None:
+      out = self._tensordot_ordered(a, b, axes, result_order)
+      return out if allow_swap else out[:3]
     out = self._tensordot_impl(a, b, axes, free_order_a, free_order_b, allow_swap)
     return out if allow_swap else out[:3]
+
+  def _tensordot_ordered(self, a, b, axes, result_order):
+    """`tensordot_planned` with `result_order`: (tensor in that order, natural free_a, natural free_b, False)"""
+    a = a if isinstance(a, DeviceTensor) else self.convert_to_tensor(a)
+    b = b if isinstance(b, DeviceTensor) else self.convert_to_tensor(b)
+    axes_a, axes_b = self._normalize_axes(a, b, axes)
+    free_a = [i for i in range(a.ndim) if i not in axes_a]
+    free_b = [i for i in range(b.ndim) if i not in axes_b]
+    order = [int(p) for p in result_order]
+    if sorted(order) != list(range(len(free_a) + len(free_b))):
+      raise ValueError(f"result_order {result_order} is not a permutation of the result's {len(free_a) + len(free_b)} axes")
+    if order == list(range(len(order))):      # natural order: nothing to scatter, the usual lowering as it is
+      return self._tensordot_impl(a, b, (axes_a, axes_b), None, None)[0], free_a, free_b, False
+    got = None
+    if a.code == b.code and a.code in _HALF and self.gather_gemm and self.gather_scatter and \
+        self.half_output == "same" and axes_a:
+      got = self._tensordot_gather_scatter(a, b, axes_a, axes_b, free_a, free_b, order)
+    if got is None:
+      got = self.transpose(self._tensordot_impl(a, b, (axes_a, axes_b), None, None)[0], order)
+    return got, free_a, free_b, False
+
+  def scatter_run_bytes(self, a, b, axes, result_order):
+    """Bytes of the contiguous runs `tnh_gemm_gather_scatter` would store for this product and order, 0 where the
+    product is not one the scatter lowering takes (nothing is launched).  The contractors compare it with
+    `gather_scatter_min_run_bytes`.  As this is the question of a PLANNED path, `_tensordot_gather`'s rule for those
+    holds here too: a box made of pieces shorter than `gather_min_piece_bytes` keeps the classic lowering, whose K1 pass
+    also lays the long operand out for later products.  A small operand at an address the kernel would refuse (a sliced
+    view that is not 16-byte aligned) gives 0 as well, so that the contractors never pay the fallback's transpose to an
+    interleaved order.  (A variant forced through `tnh_gemm_set_variant`, an A/B and test knob, is not visible here:
+    with one set, an order asked for on the strength of this answer costs the usual lowering + one K1 pass.)"""
+    if not (isinstance(a, DeviceTensor) and isinstance(b, DeviceTensor) and a.code == b.code and a.code in _HALF and
+            self.gather_gemm and self.gather_scatter and self.half_output == "same" and
+            getattr(self.lib, "tnh_gemm_gather_scatter", None) is not None):
+      return 0
+    axes_a, axes_b = self._normalize_axes(a, b, axes)
+    if not axes_a:
+      return 0
+    free_a = [i for i in range(a.ndim) if i not in axes_a]
+    free_b = [i for i in range(b.ndim) if i not in axes_b]
+    plan = self._scatter_plan(a, b, axes_a, axes_b, free_a, free_b, [int(p) for p in result_order])
+    if plan is None or _gather_piece_bytes(plan[0][0], a.itemsize) < self.gather_min_piece_bytes:
+      return 0
+    small = a if plan[1] else b
+    if small.ptr % 16:
+      return 0
+    return plan[0][3] * a.itemsize
+
+  def _scatter_plan(self, a, b, axes_a, axes_b, free_a, free_b, order):
+    """The descriptors of `_tensordot_gather_scatter` for this product: ((gather descriptor, scatter descriptor, BN,
+    run elements), small_first, small operand's free axes in destination order, destination shape), or None."""
+    m = _prod(a.shape[i] for i in free_a)
+    n = _prod(b.shape[i] for i in free_b)
+    k = _prod(a.shape[i] for i in axes_a)
+    small_first = m <= n
+    ms, nl = (m, n) if small_first else (n, m)
+    if not (64 < ms <= 192 and 16 <= k <= 192 and k % 8 == 0 and nl >= self.gather_min_rows):
+      return None
+    long_ = b if small_first else a
+    small = a if small_first else b
+    if long_.pad is not None or long_.ptr % 8:
+      return None
+    # destination axis p = natural result axis order[p]: an axis of a (source 0) or of b (source 1)
+    natural = [(0, i) for i in free_a] + [(1, i) for i in free_b]
+    dest = [natural[p] for p in order]
+    shape = tuple((a, b)[src].shape[i] for src, i in dest)
+    strides = _row_major_strides(shape)
+    long_src = 1 if small_first else 0
+    out_strides = [0] * long_.ndim
+    used_s, small_strides = [], []
+    for (src, i), st in zip(dest, strides):
+      if src == long_src:
+        out_strides[i] = st
+      else:
+        used_s.append(i)
+        small_strides.append(st)
+    axes_l = axes_b if small_first else axes_a
+    plan = _scatter_descriptor(long_.shape, axes_l, out_strides, [small.shape[i] for i in used_s], small_strides)
+    if plan is None or plan[3] == 0 or plan[3] % 4:      # (run 0: an innermost axis the kernel does not store along)
+      return None
+    return plan, small_first, used_s, shape
+
+  def _tensordot_gather_scatter(self, a, b, axes_a, axes_b, free_a, free_b, order):
+    """One `tnh_gemm_gather_scatter` launch: the product `_tensordot_gather` takes (a small operand of 65 ... 192 free
+    tuples against ONE box of a long tensor read where it lies; here also with trailing contracted axes), written in
+    the axis order `order` over [free_a..., free_b...].  Only the small operand is permuted, to [its free axes in the
+    order they have in the destination, contracted axes in the long tensor's memory order].  Or None (nothing
+    launched): the caller runs the usual lowering and one transpose; results are bit-identical either way."""
+    launch = getattr(self.lib, "tnh_gemm_gather_scatter", None)
+    if launch is None:
+      return None
+    plan = self._scatter_plan(a, b, axes_a, axes_b, free_a, free_b, order)
+    if plan is None:
+      return None
+    (desc, out_desc, _, _), small_first, used_s, shape = plan
+    small, long_ = (a, b) if small_first else (b, a)
+    axes_s, axes_l = (axes_a, axes_b) if small_first else (axes_b, axes_a)
+    by_memory = sorted(range(len(axes_l)), key=lambda i: axes_l[i])
+    small = self.transpose(self._dense(small), used_s + [axes_s[i] for i in by_memory])
+    if small.ptr % 16:
+      return None
+    ms, k = _prod(small.shape[:len(used_s)]), _prod(small.shape[len(used_s):])
+    out = DeviceTensor.empty(shape, long_.code)
+    events = getattr(self, "gemm_events", None)
+    if events is not None:
+      start = _lib.Event().record()
+    status = launch(long_.code, ms, k, out.size // ms, _vp(small), k, _vp(long_), long_.size, ctypes.byref(desc),
+                    _vp(out), ctypes.byref(out_desc))
+    if status == _lib.ERR_UNSUPPORTED:
+      return None     # (a forced A/B variant, TNH_GATHER_SCATTER=0, or an alignment rule: nothing was launched)
+    _lib.check(status, "tnh_gemm_gather_scatter")
+    if events is not None:
+      events.append((start, _lib.Event().record()))
+    self.gather_scatter_launches += 1
+    return out
 
   def _tensordot_impl(self, a, b, axes, hint_a, hint_b, allow_swap=False):
     """c[free_a..., free_b...] = sum_axes a*b (abstract_backend.py:27-38).

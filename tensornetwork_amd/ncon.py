@@ -188,8 +188,18 @@ class _Engine:
         ax1 = [l1.index(l) for l in closing]
         ax2 = [l2.index(l) for l in closing]
         order = sorted(range(len(ax1)), key=lambda n: ax1[n])
-        result, u1, u2, swapped = be.tensordot_planned(t1, t2, (tuple(ax1[n] for n in order), tuple(ax2[n] for n in order)),
-                                                       o1, o2, allow_swap=True)
+        axes = (tuple(ax1[n] for n in order), tuple(ax2[n] for n in order))
+        # the gather GEMM writes any order for free (runs of `gather_scatter_min_run_bytes` and more,
+        # profiles/gather_scatter.md): all remaining labels latest-contracted first, interleaved across both operands
+        min_run = getattr(be, "gather_scatter_min_run_bytes", None)
+        if min_run is not None and hasattr(be, "scatter_run_bytes"):
+          left = [l for l in l1 if l not in closing] + [l for l in l2 if l not in closing]
+          t = [self.when.get(l, never) for l in left]
+          whole = sorted(range(len(left)), key=lambda p: -t[p] if t[p] != never else float("-inf"))
+          if whole != list(range(len(left))) and be.scatter_run_bytes(t1, t2, axes, whole) >= min_run:
+            self.ops.append((be.tensordot_planned(t1, t2, axes, result_order=whole)[0], [left[p] for p in whole]))
+            return closing
+        result, u1, u2, swapped = be.tensordot_planned(t1, t2, axes, o1, o2, allow_swap=True)
         new_labels = [l2[n] for n in u2] + [l1[n] for n in u1] if swapped else [l1[n] for n in u1] + [l2[n] for n in u2]
         self.ops.append((result, new_labels))
         return closing

@@ -643,12 +643,29 @@ def contract_between(node1: Node, node2: Node, name: Optional[str] = None,
         node1, node2, axes1, axes2, order1, order2 = node2, node1, axes2, axes1, order2, order1
         pairs = sorted(zip(axes1, axes2))
         axes1, axes2 = [p[0] for p in pairs], [p[1] for p in pairs]
-      # (the axis order of the result is bookkeeping here: the backend may put node2's axes first)
-      t, used1, used2, swapped = be.tensordot_planned(node1.tensor, node2.tensor, [axes1, axes2], order1, order2,
-                                                      allow_swap=True)
-      sources = [(node1, i) for i in used1] + [(node2, i) for i in used2]
-      if swapped:
-        sources = sources[len(used1):] + sources[:len(used1)]
+      # Where the gather GEMM can write the result in any order for free (tnh_gemm_gather_scatter, runs of at least
+      # `gather_scatter_min_run_bytes`: profiles/gather_scatter.md) ask for ALL remaining legs latest-contracted first,
+      # interleaved across both operands, instead of one order per operand.
+      min_run = getattr(be, "gather_scatter_min_run_bytes", None)
+      order = None
+      if min_run is not None and hasattr(be, "scatter_run_bytes"):
+        legs = [(node1, i) for i in range(len(node1.edges)) if i not in axes1] + \
+               [(node2, i) for i in range(len(node2.edges)) if i not in axes2]
+        when = [edge_time.get(n.edges[i], never) for n, i in legs]
+        order = sorted(range(len(legs)), key=lambda p: -when[p] if when[p] != never else float("-inf"))
+        if order == list(range(len(legs))) or \
+            be.scatter_run_bytes(node1.tensor, node2.tensor, [axes1, axes2], order) < min_run:
+          order = None
+      if order is not None:
+        t = be.tensordot_planned(node1.tensor, node2.tensor, [axes1, axes2], result_order=order)[0]
+        sources = [legs[p] for p in order]
+      else:
+        # (the axis order of the result is bookkeeping here: the backend may put node2's axes first)
+        t, used1, used2, swapped = be.tensordot_planned(node1.tensor, node2.tensor, [axes1, axes2], order1, order2,
+                                                        allow_swap=True)
+        sources = [(node1, i) for i in used1] + [(node2, i) for i in used2]
+        if swapped:
+          sources = sources[len(used1):] + sources[:len(used1)]
     else:
       t = be.tensordot(node1.tensor, node2.tensor, [axes1, axes2])
       sources = [(node1, i) for i in range(len(node1.edges)) if i not in axes1] + \
