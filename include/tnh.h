@@ -251,6 +251,28 @@ typedef struct {
 } tnh_scatter_desc;
 int tnh_gemm_gather_scatter(int dtype, int64_t Ms, int64_t K, int64_t Nl, const void* S, int64_t lds, const void* L,
                             int64_t l_elems, const tnh_gather_desc* desc, void* C, const tnh_scatter_desc* out);
+/* tnh_gemm_view with a SCATTERED EPILOGUE: the same product (same shape and alignment rules, half output of the input's
+ * dtype), written into a dense destination C whose axes are any permutation of [A's free axes..., B's free axes...].
+ * The offset of C[m][n] is rowoff(m) + coloff(n): m is a mixed-radix number over mext[0 .. nm-1] (digit 0 innermost)
+ * with mstride[d] destination elements per index of digit d, n likewise over next / nstride.  The destination's
+ * innermost axis must be digit 0 of n with stride 1; `run` is the number of consecutive n whose elements are
+ * consecutive (that digit's extent times the extents of the digits of n that chain onto it) and must be a multiple of
+ * 4: 16-byte stores when it is a multiple of 8, 8-byte stores otherwise (C aligned to the store).  c_elems = M * N.
+ * TNH_ERR_INVALID when the extents do not multiply to M and N, `run` is not that number, or the destination is not a
+ * bijection onto [0, c_elems).  TNH_ERR_UNSUPPORTED, nothing launched: an innermost axis on the M side, a run that is
+ * no multiple of 4, more than 6 digits on a side, a k-major A, or operands whose rows the lean loop cannot address.
+ * The tail split of tnh_gemm_view is never taken.  Results are bit-identical to tnh_gemm_view (without its tail split)
+ * + tnh_permute.  Kernel names: those of tnh_gemm_view + "_scatter_v16" / "_scatter_v8" (bytes per store). */
+#define TNH_CVIEW_MAX_DIGITS 6
+typedef struct {
+  int32_t nm, nn;
+  int32_t mext[TNH_CVIEW_MAX_DIGITS], next[TNH_CVIEW_MAX_DIGITS];
+  int64_t mstride[TNH_CVIEW_MAX_DIGITS], nstride[TNH_CVIEW_MAX_DIGITS];
+  int64_t run;
+  int64_t c_elems;
+} tnh_cview_desc;
+int tnh_gemm_view_scatter(int dtype, int64_t M, int64_t N, int64_t K, const void* A, const tnh_operand_view* va,
+                          const void* B, const tnh_operand_view* vb, void* C, const tnh_cview_desc* out);
 const char* tnh_gemm_last_kernel(void);
 /* Force a variant ("auto", "generic", "valu", "bf16_128", "bf16_256", "bf16_256pp", "bf16_ragged*"),
  * optionally followed by A/B knobs ":r<d>" (tile order: 1 = super-tiles shared by the XCDs, 0 / 2 / 3 / 4 =

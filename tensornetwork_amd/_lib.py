@@ -53,6 +53,15 @@ class ScatterDesc(ctypes.Structure):
               ("ns", c_int32), ("c_elems", c_int64)]
 
 
+CVIEW_MAX_DIGITS = 6
+
+class CViewDesc(ctypes.Structure):
+  """tnh_cview_desc (include/tnh.h): where tnh_gemm_view_scatter writes C[m][n], digit by digit (innermost first)."""
+  _fields_ = [("nm", c_int32), ("nn", c_int32), ("mext", c_int32 * CVIEW_MAX_DIGITS), ("next", c_int32 * CVIEW_MAX_DIGITS),
+              ("mstride", c_int64 * CVIEW_MAX_DIGITS), ("nstride", c_int64 * CVIEW_MAX_DIGITS),
+              ("run", c_int64), ("c_elems", c_int64)]
+
+
 _I64P = POINTER(c_int64)
 _I32P = POINTER(c_int32)
 
@@ -104,6 +113,8 @@ SIGNATURES = {
                                         POINTER(GatherDesc), c_void_p, POINTER(ScatterDesc)]),
     "tnh_gemm_view": (c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, POINTER(OperandView),
                               c_void_p, POINTER(OperandView), c_void_p, c_int64]),
+    "tnh_gemm_view_scatter": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, POINTER(OperandView),
+                                      c_void_p, POINTER(OperandView), c_void_p, POINTER(CViewDesc)]),
     "tnh_complex_expand": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int]),
     "tnh_gemm_last_kernel": (c_char_p, []),
     "tnh_gemm_set_variant": (c_int, [c_char_p]),

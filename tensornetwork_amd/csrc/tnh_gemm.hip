@@ -40,6 +40,8 @@ int gemm_bf16_fast(int in_dt, int out_dt, int variant, int transA, int transB, i
 
 int gemm_bf16_view(int in_dt, int out_dt, int64_t M, int64_t N, int64_t K, const void* A, const OpView& va,
                    const void* B, const OpView& vb, void* C, int64_t ldc, const char** name);
+int gemm_bf16_view_scatter(int in_dt, int64_t M, int64_t N, int64_t K, const void* A, const OpView& va, const void* B,
+                           const OpView& vb, void* C, const tnh_cview_desc* out, const char** name);
 
 // provided by tnh_gemm_gather.hip
 int gemm_gather(int dtype, int64_t Ms, int64_t K, int64_t Nl, const void* S, int64_t lds, const void* L,
@@ -1133,6 +1135,14 @@ int tnh_complex_expand(void* dst, const void* src, int64_t K, int64_t N, int64_t
   return TNH_OK;
 }
 
+static bool view_from_abi(const tnh_operand_view* v, int64_t K, OpView* o) {
+  if (v->k0 <= 0 || v->r0 <= 0 || v->k0 % 32 != 0 || K % v->k0 != 0) return false;
+  o->r0 = v->r0; o->sr0 = v->sr0; o->sr1 = v->sr1;
+  o->sk0 = v->sk0; o->sk1 = v->sk1;
+  o->tpi = (int)(v->k0 / 32);
+  return v->k0 / 32 < (int64_t(1) << 30);
+}
+
 int tnh_gemm_view(int in_dtype, int out_dtype, int64_t M, int64_t N, int64_t K, const void* A,
                   const tnh_operand_view* va, const void* B, const tnh_operand_view* vb, void* C, int64_t ldc) {
   TNH_NEED_INIT();
@@ -1140,13 +1150,7 @@ int tnh_gemm_view(int in_dtype, int out_dtype, int64_t M, int64_t N, int64_t K, 
   TNH_REQUIRE(out_dtype == in_dtype || out_dtype == TNH_F32, "tnh_gemm_view: bad output dtype %d", out_dtype);
   TNH_REQUIRE(M > 0 && N > 0 && K > 0 && A && B && C && va && vb, "tnh_gemm_view: bad arguments");
   TNH_REQUIRE(ldc >= N, "ldc (%lld) < N (%lld)", (long long)ldc, (long long)N);
-  auto conv = [](const tnh_operand_view* v, int64_t K, OpView* o) -> bool {
-    if (v->k0 <= 0 || v->r0 <= 0 || v->k0 % 32 != 0 || K % v->k0 != 0) return false;
-    o->r0 = v->r0; o->sr0 = v->sr0; o->sr1 = v->sr1;
-    o->sk0 = v->sk0; o->sk1 = v->sk1;
-    o->tpi = (int)(v->k0 / 32);
-    return v->k0 / 32 < (int64_t(1) << 30);
-  };
+  const auto conv = view_from_abi;
   if (g_variant != 0) {   // a kernel forced through tnh_gemm_set_variant (tests, A/B): the caller's fallback path runs it
     set_error("tnh_gemm_view: a GEMM variant is forced");
     return TNH_ERR_UNSUPPORTED;
@@ -1158,6 +1162,26 @@ int tnh_gemm_view(int in_dtype, int out_dtype, int64_t M, int64_t N, int64_t K, 
   }
   const char* name = nullptr;
   int rc = gemm_bf16_view(in_dtype, out_dtype, M, N, K, A, a, B, b, C, ldc, &name);
+  if (rc == TNH_OK) g_last_kernel = name;
+  return rc;
+}
+
+int tnh_gemm_view_scatter(int dtype, int64_t M, int64_t N, int64_t K, const void* A, const tnh_operand_view* va,
+                          const void* B, const tnh_operand_view* vb, void* C, const tnh_cview_desc* out) {
+  TNH_NEED_INIT();
+  TNH_REQUIRE(dtype == TNH_BF16 || dtype == TNH_F16, "tnh_gemm_view_scatter: bf16 / f16 only (got %d)", dtype);
+  TNH_REQUIRE(M > 0 && N > 0 && K > 0 && A && B && C && va && vb && out, "tnh_gemm_view_scatter: bad arguments");
+  if (g_variant != 0) {   // a kernel forced through tnh_gemm_set_variant (tests, A/B): the caller's fallback path runs it
+    set_error("tnh_gemm_view_scatter: a GEMM variant is forced");
+    return TNH_ERR_UNSUPPORTED;
+  }
+  OpView a, b;
+  if (!view_from_abi(va, K, &a) || !view_from_abi(vb, K, &b)) {
+    set_error("tnh_gemm_view_scatter: the inner contraction run of an operand is not a multiple of 32 that divides K");
+    return TNH_ERR_UNSUPPORTED;
+  }
+  const char* name = nullptr;
+  const int rc = gemm_bf16_view_scatter(dtype, M, N, K, A, a, B, b, C, out, &name);
   if (rc == TNH_OK) g_last_kernel = name;
   return rc;
 }

@@ -21,6 +21,7 @@
 //
 // MFMA roofline: 2*M*N*K flop against 2.5 PFLOP/s dense bf16.
 #include "tnh_gemm_nt.h"
+#include "tnh_gemm_view_scatter.h"
 #include <type_traits>
 #include <utility>
 
@@ -359,8 +360,12 @@ __device__ __forceinline__ void lds_frag_tr(uint4& dst, unsigned addr) {
 //      (profiles/r05_gemm_headline_plain_vs_view.jsonl) -- which is why the view launcher picks the cheapest walk
 //      the operands allow.  Same MFMA sequence in all three: bit-identical results.
 template <bool IS_BF16, bool OUT_F32, bool TWO, bool M32 = false, bool VIEW = false, bool A_KM = false,
-          bool B_KN = false, int SCHED = 0, int KW = 0>
-__global__ __launch_bounds__(512) void gemm_nt_pp_kernel(NtArgs p) {
+          bool B_KN = false, int SCHED = 0, int KW = 0, int SCAT = 0>
+__global__ __launch_bounds__(512) void gemm_nt_pp_kernel(std::conditional_t<SCAT != 0, NtScatArgs, NtArgs> p) {
+  // SCAT = 8 / 4 (tnh_gemm_view_scatter): the tile is stored through the scattered epilogue of tnh_gemm_view_scatter.h
+  // (16-byte / 8-byte stores) instead of store_wave_tile.  Lean view loops with K-contiguous A and half output only.
+  static_assert(SCAT == 0 || ((SCAT == 8 || SCAT == 4) && VIEW && SCHED == 3 && !OUT_F32 && !A_KM && (!B_KN || KW == 1)),
+                "scattered epilogue: lean view loops, K-contiguous operands or the whole-tile k-major B, half output");
   static_assert(KW == 0 || (VIEW && !A_KM && (!B_KN || (SCHED == 3 && KW == 1))),
                 "the tile-granular K walks: K-contiguous view operands, or (lean loop, KW = 1) a k-major B");
   static_assert(!VIEW || (TWO && !M32), "view kernels use the 2-phase 16x16x32 schedule");
@@ -1129,7 +1134,13 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(NtArgs p) {
   {
   const int64_t m0 = em0, n0 = en0;
   char* Cb = (char*)p.C + (int64_t)blockIdx.y * p.sC * (OUT_F32 ? 4 : 2);
-  if constexpr (!M32) {
+  if constexpr (SCAT != 0) {
+    // a table per wave, outside the staging buffers (the next tile's loads are already landing there); no barrier.
+    // The early start rests on the store count the epilogue itself returns.
+    __shared__ int64_t cview_tab[8][CVIEW_TAB];
+    const int stores = store_wave_tile_cview<IS_BF16, SCAT>(acc, p, Cb, m0, n0, wr * 128, wc * 64, lane, cview_tab[wid]);
+    pend = p.epi_early ? stores : 0;
+  } else if constexpr (!M32) {
     store_wave_tile<IS_BF16, OUT_F32, 8, 4>(acc, p, Cb, m0, n0, BM, BN, wr * 128, wc * 64, lane);
     // how many store instructions that was, where the count is static (store_wave_tile: the 16-byte half path, the
     // float4 path of a full f32 tile); anything else is waited for in full
@@ -1584,8 +1595,10 @@ static bool view_ok(const OpView& v, int64_t rows, int64_t K, const void* base, 
   return ok;
 }
 
-int gemm_bf16_view(int in_dt, int out_dt, int64_t M, int64_t N, int64_t K, const void* A, const OpView& va,
-                   const void* B, const OpView& vb, void* C, int64_t ldc, const char** name) {
+// Shape and alignment rules of the view GEMM, its argument block and the cheapest K walk the operands allow: shared by
+// gemm_bf16_view and gemm_bf16_view_scatter.  TNH_ERR_UNSUPPORTED (error set) when a rule fails.
+static int view_setup(int64_t M, int64_t N, int64_t K, const void* A, const OpView& va, const void* B, const OpView& vb,
+                      void* C, int64_t ldc, NtArgs& p, int& kw) {
   const bool big = (M >= 256 && N >= 256) && (((M + 255) / 256) * ((N + 255) / 256) >= 192);
   if (!big || K % 64 != 0 || K < 128 || ldc % 4 != 0 || ((uintptr_t)C % 16) != 0 || M >= (int64_t(1) << 31) ||
       N >= (int64_t(1) << 31)) {
@@ -1593,7 +1606,6 @@ int gemm_bf16_view(int in_dt, int out_dt, int64_t M, int64_t N, int64_t K, const
     return TNH_ERR_UNSUPPORTED;
   }
   if (!view_ok(va, M, K, A, "A") || !view_ok(vb, N, K, B, "B")) return TNH_ERR_UNSUPPORTED;
-  NtArgs p;
   p.va = va;
   p.vb = vb;
   if (p.va.r0 > M) p.va.r0 = M;   // single-level rows: keep the 32-bit row split in range
@@ -1613,12 +1625,12 @@ int gemm_bf16_view(int in_dt, int out_dt, int64_t M, int64_t N, int64_t K, const
   const int64_t nwg = (int64_t)p.tiles_m * p.tiles_n;
   TNH_REQUIRE(nwg < (int64_t(1) << 24), "GEMM grid too large");
   const bool a_km = (va.sk0 != 1), b_kn = (vb.sk0 != 1);
-  const bool is_bf16 = (in_dt == TNH_BF16), out_f32 = (out_dt == TNH_F32);
   p.kslice_tiles = 0;
   p.m_off = 0;
+  p.lean_rel_a = p.lean_rel_b = 0;
   // The cheapest K walk both operands allow (kernel header, KW): 2 = one contiguous contraction run each (a run that
   // continues seamlessly into the next counts), 1 = runs that are multiples of 64, 0 = half-K-tile walk.
-  int kw = 0;
+  kw = 0;
   if (!a_km && !b_kn) {
     auto contiguous = [&](OpView& v) {
       const bool yes = (int64_t)v.tpi * 32 >= K || v.sk1 == (int64_t)v.tpi * 32;
@@ -1645,6 +1657,18 @@ int gemm_bf16_view(int in_dt, int out_dt, int64_t M, int64_t N, int64_t K, const
     kw = (p.va.tpi % 2 == 0 && p.vb.tpi % 2 == 0) ? 1 : 0;
     if (g_opt_kwalk >= 0 && kw > g_opt_kwalk) kw = g_opt_kwalk;
   }
+  return TNH_OK;
+}
+
+int gemm_bf16_view(int in_dt, int out_dt, int64_t M, int64_t N, int64_t K, const void* A, const OpView& va,
+                   const void* B, const OpView& vb, void* C, int64_t ldc, const char** name) {
+  NtArgs p;
+  int kw = 0;
+  const int setup_rc = view_setup(M, N, K, A, va, B, vb, C, ldc, p, kw);
+  if (setup_rc != TNH_OK) return setup_rc;
+  const bool a_km = (va.sk0 != 1), b_kn = (vb.sk0 != 1);
+  const bool is_bf16 = (in_dt == TNH_BF16), out_f32 = (out_dt == TNH_F32);
+  const int64_t nwg = (int64_t)p.tiles_m * p.tiles_n;
   auto launch = [&](const NtArgs& q, unsigned gy, bool f32_out) {
     const dim3 grid(pp_grid_x((int64_t)q.tiles_m * q.tiles_n, gy), gy);
     if (a_km && b_kn) launch_pp_view_t<true, true>(is_bf16, f32_out, grid, q);
@@ -1722,6 +1746,131 @@ int gemm_bf16_view(int in_dt, int out_dt, int64_t M, int64_t N, int64_t K, const
   }
   launch(p, 1, out_f32);
   TNH_LAUNCH_CHECK();
+  return TNH_OK;
+}
+
+// ---- view GEMM with a scattered epilogue (tnh_gemm_view_scatter; kernel side: tnh_gemm_view_scatter.h) ----------------
+// What the descriptor must be for the kernel to stay inside C: a BIJECTION of (m, n) onto [0, M * N).  The offset is a
+// sum of index x stride over independent digits, and such a sum is a bijection onto an interval exactly when the
+// digits, sorted by stride, form a dense mixed radix (the rule of the gather-scatter entry): no enumeration of elements.
+// Returns TNH_OK and the store width (elements), TNH_ERR_INVALID or TNH_ERR_UNSUPPORTED with *why set.
+static int cview_validate(const tnh_cview_desc& o, int64_t M, int64_t N, const void* C, int* vec, const char** why) {
+  if (o.nm > TNH_CVIEW_MAX_DIGITS || o.nn > TNH_CVIEW_MAX_DIGITS) { *why = "more than 6 digits on a side"; return TNH_ERR_UNSUPPORTED; }
+  if (o.nm < 1 || o.nn < 1) { *why = "digit count"; return TNH_ERR_INVALID; }
+  struct Digit { int64_t ext, stride; int side, d; };
+  Digit dg[2 * TNH_CVIEW_MAX_DIGITS];
+  int n = 0;
+  int64_t pm = 1, pn = 1;
+  for (int d = 0; d < o.nm; ++d) {
+    if (o.mext[d] < 1 || pm > M) { *why = "extents of m"; return TNH_ERR_INVALID; }
+    pm *= o.mext[d];
+    if (o.mext[d] > 1) dg[n++] = Digit{o.mext[d], o.mstride[d], 0, d};
+  }
+  for (int d = 0; d < o.nn; ++d) {
+    if (o.next[d] < 1 || pn > N) { *why = "extents of n"; return TNH_ERR_INVALID; }
+    pn *= o.next[d];
+    if (o.next[d] > 1) dg[n++] = Digit{o.next[d], o.nstride[d], 1, d};
+  }
+  if (pm != M || pn != N) { *why = "the extents do not multiply to M and N"; return TNH_ERR_INVALID; }
+  for (int i = 0; i < n; ++i)
+    if (dg[i].stride < 1) { *why = "non-positive destination stride"; return TNH_ERR_INVALID; }
+  for (int i = 1; i < n; ++i) {                 // by stride (ties fail the chain below)
+    const Digit x = dg[i];
+    int j = i;
+    for (; j > 0 && dg[j - 1].stride > x.stride; --j) dg[j] = dg[j - 1];
+    dg[j] = x;
+  }
+  int64_t expect = 1;
+  for (int i = 0; i < n; ++i) {
+    if (dg[i].stride != expect) { *why = "the destination is not a bijection onto [0, M * N)"; return TNH_ERR_INVALID; }
+    expect *= dg[i].ext;
+  }
+  if (expect != M * N || o.c_elems != expect) { *why = "the destination does not have M * N elements"; return TNH_ERR_INVALID; }
+  if (dg[0].side != 1) { *why = "the innermost destination axis is on the M side"; return TNH_ERR_UNSUPPORTED; }
+  // the run: the digits of n, innermost first, while they stay the innermost of the destination
+  int64_t run = 1;
+  int at = 0;
+  for (int d = 0; d < o.nn; ++d) {
+    if (o.next[d] == 1) continue;
+    if (at < n && dg[at].side == 1 && dg[at].d == d) { run *= o.next[d]; ++at; }
+    else break;
+  }
+  if (at == 0) { *why = "the innermost destination axis is not the innermost digit of n"; return TNH_ERR_UNSUPPORTED; }
+  if (o.run != run) { *why = "run is not the extent of the chained innermost digits of n"; return TNH_ERR_INVALID; }
+  if (run % 8 == 0 && ((uintptr_t)C % 16) == 0) *vec = 8;
+  else if (run % 4 == 0 && ((uintptr_t)C % 8) == 0) *vec = 4;
+  else { *why = "run not a multiple of 4 elements / destination alignment"; return TNH_ERR_UNSUPPORTED; }
+  return TNH_OK;
+}
+
+// digits innermost first -> the kernel's form (extent-1 digits dropped, magic numbers for idx < 2^31)
+static void cview_side(int nd, const int32_t* ext, const int64_t* stride, CViewSide& s) {
+  int64_t e[TNH_CVIEW_MAX_DIGITS], st[TNH_CVIEW_MAX_DIGITS];
+  int n = 0;
+  for (int d = 0; d < nd; ++d)
+    if (ext[d] > 1) { e[n] = ext[d]; st[n] = stride[d]; ++n; }
+  if (n == 0) { e[0] = 1; st[0] = 0; n = 1; }
+  s = CViewSide{};
+  s.ndiv = n - 1;
+  for (int d = 0; d < n - 1; ++d) {
+    int sh = 0;
+    while ((int64_t(1) << sh) < e[d]) ++sh;
+    s.ext[d] = (uint32_t)e[d];
+    s.sh[d] = 31 + sh;
+    s.mul[d] = (uint32_t)(((uint64_t(1) << (31 + sh)) + e[d] - 1) / e[d]);
+    s.stride[d] = st[d];
+  }
+  s.top = st[n - 1];
+}
+
+template <int KW, bool B_KN>
+static void launch_pp_view_scatter(bool is_bf16, int vec, dim3 grid, const NtScatArgs& q) {
+  const dim3 block(512);
+  if (is_bf16) {
+    if (vec == 8) hipLaunchKernelGGL((gemm_nt_pp_kernel<true, false, true, false, true, false, B_KN, 3, KW, 8>), grid, block, 0, stream(), q);
+    else hipLaunchKernelGGL((gemm_nt_pp_kernel<true, false, true, false, true, false, B_KN, 3, KW, 4>), grid, block, 0, stream(), q);
+  } else {
+    if (vec == 8) hipLaunchKernelGGL((gemm_nt_pp_kernel<false, false, true, false, true, false, B_KN, 3, KW, 8>), grid, block, 0, stream(), q);
+    else hipLaunchKernelGGL((gemm_nt_pp_kernel<false, false, true, false, true, false, B_KN, 3, KW, 4>), grid, block, 0, stream(), q);
+  }
+}
+
+// See include/tnh.h.  One launch of the lean view kernel over all of M: the tail split of gemm_bf16_view is never taken
+// here -- its split-K reduction writes a dense row-major slab, not the scattered destination (cost on the D = 12
+// network's 20736 x 1728 x 20736 product: profiles/view_scatter.md).
+int gemm_bf16_view_scatter(int in_dt, int64_t M, int64_t N, int64_t K, const void* A, const OpView& va, const void* B,
+                           const OpView& vb, void* C, const tnh_cview_desc* out, const char** name) {
+  NtScatArgs p;
+  int kw = 0;
+  int rc = view_setup(M, N, K, A, va, B, vb, C, N, p, kw);
+  if (rc != TNH_OK) return rc;
+  const char* why = nullptr;
+  int vec = 0;
+  rc = cview_validate(*out, M, N, C, &vec, &why);
+  if (rc != TNH_OK) {
+    set_error("tnh_gemm_view_scatter: %s", why);
+    return rc;
+  }
+  const bool a_km = (va.sk0 != 1), b_kn = (vb.sk0 != 1);
+  // the loop forms that have a scatter instantiation: the lean loops over K-contiguous operands (KW 0 / 1 / 2) and the
+  // whole-K-tile walk of a k-major B
+  bool lean = false;
+  if (!a_km && g_opt_phases != 7) lean = b_kn ? (kw >= 1 && lean_view_rows(p, false, false, true, true)) : lean_view_rows(p, kw == 0);
+  if (!lean) {
+    set_error("tnh_gemm_view_scatter: the loop form these operands take has no scattered epilogue");
+    return TNH_ERR_UNSUPPORTED;
+  }
+  cview_side(out->nm, out->mext, out->mstride, p.row);
+  cview_side(out->nn, out->next, out->nstride, p.col);
+  const dim3 grid(pp_grid_x((int64_t)p.tiles_m * p.tiles_n, 1), 1);
+  const bool is_bf16 = in_dt == TNH_BF16;
+  if (b_kn) launch_pp_view_scatter<1, true>(is_bf16, vec, grid, p);
+  else if (kw == 2) launch_pp_view_scatter<2, false>(is_bf16, vec, grid, p);
+  else if (kw == 1) launch_pp_view_scatter<1, false>(is_bf16, vec, grid, p);
+  else launch_pp_view_scatter<0, false>(is_bf16, vec, grid, p);
+  TNH_LAUNCH_CHECK();
+  *name = b_kn ? (vec == 8 ? "bf16_view_nn_256x256x64_pp_scatter_v16" : "bf16_view_nn_256x256x64_pp_scatter_v8")
+               : (vec == 8 ? "bf16_view_nt_256x256x64_pp_scatter_v16" : "bf16_view_nt_256x256x64_pp_scatter_v8");
   return TNH_OK;
 }
 

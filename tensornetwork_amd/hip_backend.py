@@ -310,6 +310,129 @@ def _scatter_descriptor_cached(shape, k_axes, out_strides, small_ext, small_stri
   return desc, out, bn, run
 
 
+_VIEW_SCATTER_MIN_RUN = "24"       # default of HipBackend.view_scatter_min_run_bytes (profiles/view_scatter.md)
+
+
+def _cview_descriptor(ext_a, ext_b, order, keep_a, keep_b):
+  """see _cview_descriptor_cached"""
+  return _cview_descriptor_cached(tuple(int(n) for n in ext_a), tuple(int(n) for n in ext_b),
+                                  tuple(int(p) for p in order), bool(keep_a), bool(keep_b))
+
+
+@functools.lru_cache(maxsize=512)
+def _cview_descriptor_cached(ext_a, ext_b, order, keep_a, keep_b):
+  """Destination descriptor (tnh_cview_desc, include/tnh.h) of tnh_gemm_view_scatter for a product whose operands have
+  the free extents `ext_a` / `ext_b` (natural axis order) and whose result is wanted as
+  transpose([a's free axes..., b's free axes...], order).  `keep_x`: operand x is read in place, so its rows run over
+  its free axes in natural order; an operand that takes a K1 pass anyway is permuted with its free axes in destination
+  order, which makes the runs as long as the destination allows.  The operand that owns the destination's innermost
+  axis becomes the kernel's N side (`n_is_a`: `a` does, the caller passes `b` as A and `a` as B); that axis must be the
+  last of its row axes.  Adjacent digits whose destination strides chain are merged.  Returns (descriptor, n_is_a,
+  positions of a's free axes in row order, the same for b, run elements, destination shape) or None: the innermost
+  axis is not the last row axis of an operand read in place, more than 6 digits on a side, or a run that is no multiple
+  of 4."""
+  na = len(ext_a)
+  ext = (ext_a, ext_b)
+  dest = [(0, p) if p < na else (1, p - na) for p in order]      # destination axis -> (operand, position among its free axes)
+  shape = tuple(ext[src][i] for src, i in dest)
+  stride_of = dict(zip(dest, _row_major_strides(shape)))
+  inner = [d for d in dest if ext[d[0]][d[1]] != 1]
+  if not inner:
+    return None
+  n_src = inner[-1][0]
+  used, digits = [], []
+  for src, keep in ((0, keep_a), (1, keep_b)):
+    rows = list(range(len(ext[src]))) if keep else [i for s, i in dest if s == src]
+    merged = []                                  # innermost first: [extent, destination stride]
+    for i in reversed(rows):
+      e, st = ext[src][i], stride_of[(src, i)]
+      if e == 1:
+        continue
+      if merged and st == merged[-1][0] * merged[-1][1]:
+        merged[-1][0] *= e
+      else:
+        merged.append([e, st])
+    if not merged or len(merged) > _lib.CVIEW_MAX_DIGITS:
+      return None
+    used.append(tuple(rows))
+    digits.append(merged)
+  run = digits[n_src][0][0]
+  if digits[n_src][0][1] != 1 or run % 4:
+    return None
+  out = _lib.CViewDesc()
+  m_side, n_side = digits[1 - n_src], digits[n_src]
+  out.nm, out.nn = len(m_side), len(n_side)
+  for d, (e, st) in enumerate(m_side):
+    out.mext[d], out.mstride[d] = e, st
+  for d, (e, st) in enumerate(n_side):
+    out.next[d], out.nstride[d] = e, st
+  out.run = run
+  out.c_elems = _prod(shape)
+  return out, n_src == 0, used[0], used[1], run, shape
+
+
+def _view_scatter_loop(va, m, vb, n, k):
+  """Does `tnh_gemm_view_scatter` have a loop for these operand views (A = the M side, rows m; B = the N side, rows n)?
+  The host rules of tnh_gemm_bf16.hip, so that nothing is paid for a product the entry then refuses: a K-contiguous A;
+  B K-contiguous, or k-major with contraction runs of both operands that are multiples of 64 (the whole-K-tile walk);
+  and rows the lean loop can address with 32-bit offsets (`lean_view_rows`)."""
+  if va.sk0 != 1:
+    return False
+  b_km = vb.sk0 != 1
+  run_a = k if va.k0 >= k or va.sk1 == va.k0 else va.k0              # (a run that continues seamlessly is one run)
+  run_b = k if vb.k0 >= k or vb.sk1 == vb.k0 * vb.sk0 else vb.k0
+  if b_km:
+    if run_a % 64 or run_b % 64:
+      return False
+    half_walk = False
+  else:
+    half_walk = not (run_a == k and run_b == k) and (run_a % 64 != 0 or run_b % 64 != 0)
+  lim = 1 << 31                                                      # elements (2 bytes each)
+
+  def rows_ok(v, rows, run, kmajor):
+    if v.sr0 <= 0:
+      return False
+    jump = 64 * v.sk0 if kmajor else (v.sk1 - run if half_walk and run < k else 0)
+    if jump < 0 or jump >= lim // 2:
+      return False
+    r0 = min(v.r0, rows)
+    single = r0 >= rows
+    inner = (r0 - 1) * v.sr0
+    if single or v.sr1 > inner:
+      span = (255 * v.sr0 if single else inner + (255 // r0 + 2) * v.sr1) + 64 + jump
+      if span < lim:
+        return True
+    if not single and v.sr1 < 0:
+      return False
+    whole = ((rows - 1) * v.sr0 if single else inner + ((rows - 1) // r0) * v.sr1) + 64 + jump
+    return whole < lim
+
+  return rows_ok(va, m, run_a, False) and rows_ok(vb, n, run_b, b_km)
+
+
+def _view_tail_split(m, n, k, cus):
+  """Would `tnh_gemm_view` cut the last tile rows of this product off into a split-K launch (`+tail_splitk`)?  The rule
+  of gemm_bf16_view (tnh_gemm_bf16.hip), which the scattered entry never applies."""
+  tiles_m, tiles_n, nkt = (m + 255) // 256, (n + 255) // 256, k // 64
+  nwg = tiles_m * tiles_n
+  if nwg <= cus or nkt < 96:
+    return False
+  base = (nwg + cus - 1) // cus
+  for rt in range(1, min(32, tiles_m - 1) + 1):
+    tail = rt * tiles_n
+    s = min(cus // tail, 16)
+    if s < 2:
+      continue
+    ks = (nkt + s - 1) // s
+    if ks < 8:
+      continue
+    s_eff = (nkt + ks - 1) // ks
+    cost = ((tiles_m - rt) * tiles_n + cus - 1) // cus + ((tail * s_eff + cus - 1) // cus) * ks / nkt + 0.10
+    if cost <= 0.94 * base:
+      return True
+  return False
+
+
 def _gather_piece_bytes(desc, itemsize=2):
   """bytes of the contiguous pieces of memory a box is made of (its leading digits while each starts where the
   one before ends)"""
@@ -450,6 +573,23 @@ class HipBackend(BackendBase):
     _min_run = os.environ.get("TNH_GATHER_SCATTER_MIN_RUN", "24")      # "off": the contractors never ask
     self.gather_scatter_min_run_bytes = int(_min_run) if _min_run.isdigit() else None
     self.gather_scatter_launches = 0     # tnh_gemm_gather_scatter launches
+    # The same for the products of the 256 x 256 view GEMM (tnh_gemm_view_scatter; TNH_VIEW_SCATTER=0: off).
+    # `view_scatter_min_run_bytes`: the contiguous run of the destination from which the backend takes the scattered
+    # form at all (None: never) -- see profiles/view_scatter.md for where the value comes from.
+    self.view_scatter = os.environ.get("TNH_VIEW_SCATTER", "1") != "0"
+    _min_run = os.environ.get("TNH_VIEW_SCATTER_MIN_RUN", _VIEW_SCATTER_MIN_RUN)      # "off": never
+    self.view_scatter_min_run_bytes = int(_min_run) if _min_run.isdigit() else None
+    self.view_scatter_launches = 0       # tnh_gemm_view_scatter launches
+    # A product whose last, mostly empty wave of tiles `tnh_gemm_view` would split over K (`_view_tail_split`: the rule
+    # of gemm_bf16_view) keeps the usual lowering, because the scattered entry never splits: 20736 x 1728 x 20736 ran
+    # 1.33 ms scattered against 1.09-1.14 ms for tail split + K1 pass (profiles/view_scatter.md).
+    # TNH_VIEW_SCATTER_KEEP_TAIL_SPLIT=0: scatter those too.
+    self.view_scatter_keep_tail_split = os.environ.get("TNH_VIEW_SCATTER_KEEP_TAIL_SPLIT", "1") != "0"
+    self._cus = None
+    # The contractors (`contract_between`, `ncon`, `contract_path`) put their question to `scatter_run_bytes` only while
+    # `gather_scatter_min_run_bytes` is set, and compare the answer with it: TNH_GATHER_SCATTER_MIN_RUN=off keeps them
+    # from asking for these products too, and a `view_scatter_min_run_bytes` below it takes effect only for direct
+    # callers of `tensordot_planned(..., result_order=...)`.
     self.permutes_absorbed = 0   # tnh_gemm_view launches
     self.permute_launches = 0    # K1 launches (transpose)
     self._direct_launches = type(self).transpose is HipBackend.transpose and type(self)._gemm is HipBackend._gemm
@@ -855,6 +995,8 @@ class HipBackend(BackendBase):
     if a.code == b.code and a.code in _HALF and self.gather_gemm and self.gather_scatter and \
         self.half_output == "same" and axes_a:
       got = self._tensordot_gather_scatter(a, b, axes_a, axes_b, free_a, free_b, order)
+    if got is None and axes_a:
+      got = self._tensordot_view_scatter(a, b, axes_a, axes_b, free_a, free_b, order)
     if got is None:
       got = self.transpose(self._tensordot_impl(a, b, (axes_a, axes_b), None, None)[0], order)
     return got, free_a, free_b, False
@@ -867,17 +1009,26 @@ class HipBackend(BackendBase):
     also lays the long operand out for later products.  A small operand at an address the kernel would refuse (a sliced
     view that is not 16-byte aligned) gives 0 as well, so that the contractors never pay the fallback's transpose to an
     interleaved order.  (A variant forced through `tnh_gemm_set_variant`, an A/B and test knob, is not visible here:
-    with one set, an order asked for on the strength of this answer costs the usual lowering + one K1 pass.)"""
+    with one set, an order asked for on the strength of this answer costs the usual lowering + one K1 pass.)
+    For a product of the 256 x 256 view GEMM the answer is the run `tnh_gemm_view_scatter` would store, under
+    `_view_scatter_plan`'s rules (0 below `view_scatter_min_run_bytes`, for tail-split products and for operand forms
+    the entry has no loop for)."""
     if not (isinstance(a, DeviceTensor) and isinstance(b, DeviceTensor) and a.code == b.code and a.code in _HALF and
-            self.gather_gemm and self.gather_scatter and self.half_output == "same" and
-            getattr(self.lib, "tnh_gemm_gather_scatter", None) is not None):
+            self.half_output == "same"):
       return 0
     axes_a, axes_b = self._normalize_axes(a, b, axes)
     if not axes_a:
       return 0
     free_a = [i for i in range(a.ndim) if i not in axes_a]
     free_b = [i for i in range(b.ndim) if i not in axes_b]
-    plan = self._scatter_plan(a, b, axes_a, axes_b, free_a, free_b, [int(p) for p in result_order])
+    order = [int(p) for p in result_order]
+    # the products of the view GEMM (tnh_gemm_view_scatter): the run, from `view_scatter_min_run_bytes` on
+    vplan = self._view_scatter_plan(a, b, axes_a, axes_b, free_a, free_b, order)
+    if vplan is not None:
+      return vplan[0][4] * a.itemsize
+    if not (self.gather_gemm and self.gather_scatter and getattr(self.lib, "tnh_gemm_gather_scatter", None) is not None):
+      return 0
+    plan = self._scatter_plan(a, b, axes_a, axes_b, free_a, free_b, order)
     if plan is None or _gather_piece_bytes(plan[0][0], a.itemsize) < self.gather_min_piece_bytes:
       return 0
     small = a if plan[1] else b
@@ -951,6 +1102,88 @@ class HipBackend(BackendBase):
     if events is not None:
       events.append((start, _lib.Event().record()))
     self.gather_scatter_launches += 1
+    return out
+
+  def _view_scatter_plan(self, a, b, axes_a, axes_b, free_a, free_b, order):
+    """What `_tensordot_view_scatter` would do for this product and order, nothing launched: (`_cview_descriptor`'s
+    values, (a, its view, its K1 pass or None), the same for b) with the operand choice of `_view_choice`, or None --
+    the form is off, the product is not the view GEMM's (or one a gather lowering may take, or one whose tail the view
+    GEMM would split over K), the destination is one the kernel does not store, its run is below
+    `view_scatter_min_run_bytes`, or the operand views are ones the entry has no loop for.  Host arithmetic only; on
+    the contractors' path it runs twice per product (`scatter_run_bytes`, then the lowering): tensors are not kept
+    alive in a cache for it."""
+    if not (self.view_scatter and self.view_scatter_min_run_bytes is not None and self.absorb_transposes and
+            a.code == b.code and a.code in _HALF and self.half_output == "same" and
+            getattr(self.lib, "tnh_gemm_view_scatter", None) is not None):
+      return None
+    m = _prod(a.shape[i] for i in free_a)
+    n = _prod(b.shape[i] for i in free_b)
+    k = _prod(a.shape[i] for i in axes_a)
+    if min(m, n) <= self.gather_max_small or (self.view_scatter_keep_tail_split and
+                                              _view_tail_split(m, n, k, self._compute_units())):
+      return None
+    choice = self._view_choice(a, b, axes_a, axes_b, free_a, free_b, m, n, k)
+    if choice is None:
+      return None
+    ka, kb, va, vb = choice
+    plan = _cview_descriptor([a.shape[i] for i in free_a], [b.shape[i] for i in free_b], order, va is not None,
+                             vb is not None)
+    if plan is None or plan[4] * a.itemsize < self.view_scatter_min_run_bytes:
+      return None
+    # the K1 pass of an operand that is not read in place: (tensor, permutation, view of the result), not run yet
+    pass_a = pass_b = None
+    if va is None:
+      pass_a = self._k_blocked_plan(a, [free_a[i] for i in plan[2]], ka, m, k)
+      va = pass_a[2]
+    if vb is None:
+      pass_b = self._k_blocked_plan(b, [free_b[i] for i in plan[3]], kb, n, k)
+      vb = pass_b[2]
+    # what the entry would refuse (a k-major operand on the M side, a k-major N side without the whole-K-tile walk,
+    # rows the lean loop cannot address) is refused here, before a pass is paid or a contractor asks for the order
+    if not (_view_scatter_loop(vb, n, va, m, k) if plan[1] else _view_scatter_loop(va, m, vb, n, k)):
+      return None
+    return plan, (a, va, pass_a), (b, vb, pass_b)
+
+  def _compute_units(self):
+    """CUs of the device (what the view GEMM's tail split is sized by)"""
+    if self._cus is None:
+      cus, hbm = ctypes.c_int(0), ctypes.c_int64(0)
+      info = getattr(self.lib, "tnh_device_info", None)
+      ok = info is not None and info(ctypes.create_string_buffer(64), 64, ctypes.byref(cus), ctypes.byref(hbm)) == 0
+      self._cus = cus.value if ok and cus.value > 0 else 256
+    return self._cus
+
+  def _tensordot_view_scatter(self, a, b, axes_a, axes_b, free_a, free_b, order):
+    """One `tnh_gemm_view_scatter` launch: the product `_tensordot_in_place` takes, with the same operands read in
+    place, written in the axis order `order` over [free_a..., free_b...] by the GEMM's own epilogue.  The operand that
+    owns the destination's innermost axis is the kernel's N side (`b` is passed as A and `a` as B when it is `a`); an
+    operand that takes a K1 pass anyway is permuted to [its free axes in destination order, contracted axes].  Or None
+    (no GEMM launched): the caller runs the usual lowering and one transpose; results are bit-identical either way."""
+    plan = self._view_scatter_plan(a, b, axes_a, axes_b, free_a, free_b, order)
+    if plan is None:
+      return None
+    (desc, n_is_a, _, _, _, shape), (a, va, pass_a), (b, vb, pass_b) = plan
+    m = _prod(a.shape[i] for i in free_a)
+    n = _prod(b.shape[i] for i in free_b)
+    k = _prod(a.shape[i] for i in axes_a)
+    if pass_a is not None:
+      a = self.transpose(pass_a[0], pass_a[1])
+    if pass_b is not None:
+      b = self.transpose(pass_b[0], pass_b[1])
+    out = DeviceTensor.empty(shape, a.code)
+    if n_is_a:
+      a, va, m, b, vb, n = b, vb, n, a, va, m
+    events = getattr(self, "gemm_events", None)
+    if events is not None:
+      start = _lib.Event().record()
+    status = self.lib.tnh_gemm_view_scatter(a.code, m, n, k, _vp(a), ctypes.byref(va), _vp(b), ctypes.byref(vb),
+                                            _vp(out), ctypes.byref(desc))
+    if status == _lib.ERR_UNSUPPORTED:
+      return None     # (a forced A/B variant or knob: the plan has already refused what the entry's own rules refuse)
+    _lib.check(status, "tnh_gemm_view_scatter")
+    if events is not None:
+      events.append((start, _lib.Event().record()))
+    self.view_scatter_launches += 1
     return out
 
   def _tensordot_impl(self, a, b, axes, hint_a, hint_b, allow_swap=False):
@@ -1255,6 +1488,48 @@ class HipBackend(BackendBase):
     viewed trivially.  Returns (tensor, used_free_a, used_free_b).  `wide` (the caller's attempt at the wide gather
     kernel, or None) is called where the long operand is about to be permuted; when it delivers, its four values
     (`_tensordot_gather`'s) are returned instead."""
+    choice = self._view_choice(a, b, axes_a, axes_b, free_a, free_b, m, n, k, hint_a, hint_b)
+    if choice is None:
+      return None
+    ka, kb, va, vb = choice
+    if wide is not None and (vb if m <= n else va) is None:
+      # about to K1-permute the long operand: the wide gather kernel reads it where it lies instead (its result is
+      # returned as `_tensordot_gather` gives it, four values)
+      got = wide()
+      if got is not None:
+        return got
+    used_a, used_b = list(free_a), list(free_b)
+    if va is None:
+      if hint_a is not None and sorted(hint_a) == sorted(free_a):
+        used_a = [int(i) for i in hint_a]
+      a, va = self._k_blocked(a, used_a, ka, m, k)
+    if vb is None:
+      if hint_b is not None and sorted(hint_b) == sorted(free_b):
+        used_b = [int(i) for i in hint_b]
+      b, vb = self._k_blocked(b, used_b, kb, n, k)
+    out_code = _lib.F32 if self.half_output == "float32" else a.code
+    ldc = self._result_pitch(m, n, 4 if out_code == _lib.F32 else 2)
+    if ldc == n:
+      out = DeviceTensor.empty((m, n), out_code)
+    else:
+      out = DeviceTensor.empty((m * ldc,), out_code).as_rows(m, n, ldc)
+    events = getattr(self, "gemm_events", None)
+    if events is not None:
+      start = _lib.Event().record()
+    status = self.lib.tnh_gemm_view(a.code, out_code, m, n, k, _vp(a), ctypes.byref(va), _vp(b), ctypes.byref(vb),
+                                    _vp(out), ldc)
+    if status == _lib.ERR_UNSUPPORTED:
+      return None     # (a forced A/B variant, or an alignment rule: nothing was launched)
+    _lib.check(status, "tnh_gemm_view")
+    if events is not None:
+      events.append((start, _lib.Event().record()))
+    self.permutes_absorbed += 1
+    return out, used_a, used_b
+
+  def _view_choice(self, a, b, axes_a, axes_b, free_a, free_b, m, n, k, hint_a=None, hint_b=None):
+    """The operand choice of the view GEMM lowerings (`_tensordot_in_place`, `_tensordot_view_scatter`): nothing is
+    launched.  Returns (ka, kb, va, vb) -- the contracted axes of a / b in the chosen K order and the view of each
+    operand that is read in place (None: it takes a K1 pass) -- or None when the product is not the view GEMM's."""
     if m < 256 or n < 256 or ((m + 255) // 256) * ((n + 255) // 256) < 192 or k % 64 or k < 128:
       return None
     if a.ptr % 16 or b.ptr % 16:
@@ -1334,40 +1609,7 @@ class HipBackend(BackendBase):
       cost = (a.nbytes if va is None else 0) + (b.nbytes if vb is None else 0)
       if best is None or cost < best[0]:
         best = (cost, ka, kb, va, vb)
-    _, ka, kb, va, vb = best
-    if wide is not None and (vb if m <= n else va) is None:
-      # about to K1-permute the long operand: the wide gather kernel reads it where it lies instead (its result is
-      # returned as `_tensordot_gather` gives it, four values)
-      got = wide()
-      if got is not None:
-        return got
-    used_a, used_b = list(free_a), list(free_b)
-    if va is None:
-      if hint_a is not None and sorted(hint_a) == sorted(free_a):
-        used_a = [int(i) for i in hint_a]
-      a, va = self._k_blocked(a, used_a, ka, m, k)
-    if vb is None:
-      if hint_b is not None and sorted(hint_b) == sorted(free_b):
-        used_b = [int(i) for i in hint_b]
-      b, vb = self._k_blocked(b, used_b, kb, n, k)
-    out_code = _lib.F32 if self.half_output == "float32" else a.code
-    ldc = self._result_pitch(m, n, 4 if out_code == _lib.F32 else 2)
-    if ldc == n:
-      out = DeviceTensor.empty((m, n), out_code)
-    else:
-      out = DeviceTensor.empty((m * ldc,), out_code).as_rows(m, n, ldc)
-    events = getattr(self, "gemm_events", None)
-    if events is not None:
-      start = _lib.Event().record()
-    status = self.lib.tnh_gemm_view(a.code, out_code, m, n, k, _vp(a), ctypes.byref(va), _vp(b), ctypes.byref(vb),
-                                    _vp(out), ldc)
-    if status == _lib.ERR_UNSUPPORTED:
-      return None     # (a forced A/B variant, or an alignment rule: nothing was launched)
-    _lib.check(status, "tnh_gemm_view")
-    if events is not None:
-      events.append((start, _lib.Event().record()))
-    self.permutes_absorbed += 1
-    return out, used_a, used_b
+    return best[1:]
 
   def _k_blocked(self, t, free, kax, rows, k):
     """The K1 pass that brings an operand of the view GEMM to K-contiguous form, and the view of its result.  Normally
@@ -1378,6 +1620,12 @@ class HipBackend(BackendBase):
     766 -> 1480; x 2^19: 1294 -> 1532; profiles/r06_k_blocked_operands.md).  The inner run is the shortest suffix
     of the contracted axes that is a multiple of 64 and at least 512 long (a single long contracted axis is split by
     a reshape first: metadata only)."""
+    t, perm, view = self._k_blocked_plan(t, free, kax, rows, k)
+    return self.transpose(t, perm), view
+
+  def _k_blocked_plan(self, t, free, kax, rows, k):
+    """`_k_blocked` without the pass: (the tensor, re-viewed where an axis is split; the permutation; the view of the
+    pass's result)."""
     if self.k_blocked_permutes and k * t.itemsize >= self.k_blocked_min_row_bytes and rows >= 64:
       shape = list(t.shape)
       free, kax = list(free), list(kax)
@@ -1397,8 +1645,8 @@ class HipBackend(BackendBase):
       for s in range(len(kax) - 1, 0, -1):
         inner *= shape[kax[s]]
         if inner % 64 == 0 and inner >= 512:
-          return self.transpose(t, kax[:s] + free + kax[s:]), _lib.OperandView(rows, inner, 0, inner, 1, rows * inner)
-    return self.transpose(t, list(free) + list(kax)), _lib.OperandView(rows, k, 0, k, 1, 0)
+          return t, kax[:s] + free + kax[s:], _lib.OperandView(rows, inner, 0, inner, 1, rows * inner)
+    return t, list(free) + list(kax), _lib.OperandView(rows, k, 0, k, 1, 0)
 
   def _complex_gemm(self, a, b, trans_a, trans_b, m, n, k):
     """complex64 / complex128 product on the f32 / f64 matrix cores: the interleaved (re, im)
