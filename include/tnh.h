@@ -239,7 +239,11 @@ int tnh_gemm_gather_plan(const tnh_gather_desc* desc, int64_t K, int64_t Nl, int
  * rule of tnh_gemm_gather (or TNH_GATHER_SCATTER=0).  TNH_ERR_INVALID when the described destination is not a bijection
  * onto [0, Ms * Nl).  Results are bit-identical to tnh_gemm_gather + tnh_permute (same MFMA sequence).
  * Kernel names: bf16_gather_scatter_{64,48}xS_v{16,8} (staged [BN][Ms], runs along the small operand's axes) and
- * bf16_gather_scatter_Sx{64,48}_v{16,8} (staged [Ms][BN], runs along the box rows); v = bytes per store. */
+ * bf16_gather_scatter_Sx{64,48}_v{16,8} (staged [Ms][BN], runs along the box rows); v = bytes per store.
+ * Wide form (192 < Ms <= 256, one box of 8 <= K <= 256 indices, kl_ext == 1; kernel names
+ * bf16_gather_scatter_wide_{64,48}xS_v{16,8} and bf16_gather_scatter_wide_Sx{64,48}_v{16,8}): the same rules, S addressed
+ * in 64 bits (no bound on Ms * lds), results bit-identical to the wide form of tnh_gemm_gather + tnh_permute.  Off,
+ * TNH_ERR_UNSUPPORTED, with TNH_GATHER_SCATTER=0 or TNH_GATHER_WIDE=0; Ms <= 192 with K > 192 is unsupported. */
 #define TNH_SCATTER_MAX_SMALL_DIGITS 8
 typedef struct {
   int64_t omult[TNH_GATHER_MAX_DIGITS];

@@ -1,6 +1,6 @@
 // Pieces shared by the gather GEMM kernels (tnh_gemm_gather.hip: small operands of up to 192 rows;
-// tnh_gemm_gather_wide.hip: 193 ... 256 rows; tnh_gemm_gather_scatter.hip: up to 192 rows, result written in the
-// consumer's axis order): the descriptor arithmetic and the argument block.
+// tnh_gemm_gather_wide.hip: 193 ... 256 rows; tnh_gemm_gather_scatter.hip / tnh_gemm_gather_scatter_wide.hip: the same
+// two ranges with the result written in the consumer's axis order): the descriptor arithmetic and the argument blocks.
 #pragma once
 #include "tnh_gemm_nt.h"
 
@@ -102,6 +102,60 @@ struct GatherArgs {
   int ntiles;
 };
 
+// ---- the scattered epilogue (tnh_gemm_gather_scatter.hip, tnh_gemm_gather_scatter_wide.hip)
+struct ScatterArgs {
+  GatherArgs a;          // (a.C: the destination's first element; a.ldc unused)
+  tnh_scatter_desc o;
+};
+
+// ---- destination arithmetic shared by the kernel and the host-side validation
+// Row r of a box in the mixed radix of its FREE digits (innermost first: the weights `mult` of the descriptor).
+__host__ __device__ __forceinline__ int64_t scatter_row_offset(const tnh_gather_desc& g, const tnh_scatter_desc& o, int r) {
+  int64_t off = 0;
+  unsigned rem = (unsigned)r;
+#pragma unroll
+  for (int d = 0; d < TNH_GATHER_MAX_DIGITS; ++d) {
+    if (d < g.nd && !((g.k_mask >> d) & 1)) {
+      const unsigned ext = (unsigned)g.ext[d];
+      const unsigned q = rem / ext;
+      off += (int64_t)(rem - q * ext) * o.omult[d];
+      rem = q;
+    }
+  }
+  return off;
+}
+
+// Row c of the small operand in the mixed radix of its free digits (innermost first).
+__host__ __device__ __forceinline__ int64_t scatter_col_offset(const tnh_scatter_desc& o, int c) {
+  int64_t off = 0;
+  unsigned rem = (unsigned)c;
+#pragma unroll
+  for (int d = 0; d < TNH_SCATTER_MAX_SMALL_DIGITS; ++d) {
+    if (d < o.ns) {
+      const unsigned ext = (unsigned)o.sext[d];
+      const unsigned q = rem / ext;
+      off += (int64_t)(rem - q * ext) * o.sstride[d];
+      rem = q;
+    }
+  }
+  return off;
+}
+
+__host__ __device__ __forceinline__ int64_t scatter_tile_base(const tnh_gather_desc& g, const tnh_scatter_desc& o, int tile) {
+  int64_t base = 0;
+  unsigned t = (unsigned)tile;
+#pragma unroll
+  for (int d = 0; d < TNH_GATHER_MAX_TILE_DIGITS; ++d) {
+    if (d < g.nt) {
+      const unsigned ext = (unsigned)g.text[d];
+      const unsigned q = t / ext;
+      base += (int64_t)(t - q * ext) * o.otstride[d];
+      t = q;
+    }
+  }
+  return base;
+}
+
 // provided by tnh_gemm_gather.hip: everything the kernels rely on in a descriptor, checked on the host (the last few
 // accepted ones are remembered).  Returns the tile height BN (48 / 64), or 0 with the reason in *why.
 int gather_validate_cached(const tnh_gather_desc& g, int64_t K, int64_t Nl, int64_t l_elems, const char** why);
@@ -109,5 +163,11 @@ int gather_validate_cached(const tnh_gather_desc& g, int64_t K, int64_t Nl, int6
 // provided by tnh_gemm_gather_wide.hip: 192 < Ms <= 256, one box of BN x K (K <= 256), descriptor already validated.
 // TNH_ERR_UNSUPPORTED, nothing launched, when the images do not fit the 160 KB of a CU.
 int launch_gather_wide(int bn, bool swap, bool kin, bool is_bf16, const GatherArgs& p, const char** name);
+
+// provided by tnh_gemm_gather_scatter_wide.hip: the same range with the scattered epilogue; descriptor and destination
+// already validated (`rows_long` / `vec`: staging form and elements per store, from scatter_validate).
+// TNH_ERR_UNSUPPORTED, nothing launched, outside the range or when the images do not fit the 160 KB of a CU.
+int launch_gather_scatter_wide(int bn, bool rows_long, bool kin, int vec, bool is_bf16, const ScatterArgs& q,
+                               const char** name);
 
 }  // namespace tnh

@@ -39,59 +39,6 @@
 
 namespace tnh {
 
-struct ScatterArgs {
-  GatherArgs a;          // (a.C: the destination's first element; a.ldc unused)
-  tnh_scatter_desc o;
-};
-
-// ---- destination arithmetic shared by the kernel and the host-side validation
-// Row r of a box in the mixed radix of its FREE digits (innermost first: the weights `mult` of the descriptor).
-__host__ __device__ __forceinline__ int64_t scatter_row_offset(const tnh_gather_desc& g, const tnh_scatter_desc& o, int r) {
-  int64_t off = 0;
-  unsigned rem = (unsigned)r;
-#pragma unroll
-  for (int d = 0; d < TNH_GATHER_MAX_DIGITS; ++d) {
-    if (d < g.nd && !((g.k_mask >> d) & 1)) {
-      const unsigned ext = (unsigned)g.ext[d];
-      const unsigned q = rem / ext;
-      off += (int64_t)(rem - q * ext) * o.omult[d];
-      rem = q;
-    }
-  }
-  return off;
-}
-
-// Row c of the small operand in the mixed radix of its free digits (innermost first).
-__host__ __device__ __forceinline__ int64_t scatter_col_offset(const tnh_scatter_desc& o, int c) {
-  int64_t off = 0;
-  unsigned rem = (unsigned)c;
-#pragma unroll
-  for (int d = 0; d < TNH_SCATTER_MAX_SMALL_DIGITS; ++d) {
-    if (d < o.ns) {
-      const unsigned ext = (unsigned)o.sext[d];
-      const unsigned q = rem / ext;
-      off += (int64_t)(rem - q * ext) * o.sstride[d];
-      rem = q;
-    }
-  }
-  return off;
-}
-
-__host__ __device__ __forceinline__ int64_t scatter_tile_base(const tnh_gather_desc& g, const tnh_scatter_desc& o, int tile) {
-  int64_t base = 0;
-  unsigned t = (unsigned)tile;
-#pragma unroll
-  for (int d = 0; d < TNH_GATHER_MAX_TILE_DIGITS; ++d) {
-    if (d < g.nt) {
-      const unsigned ext = (unsigned)g.text[d];
-      const unsigned q = t / ext;
-      base += (int64_t)(t - q * ext) * o.otstride[d];
-      t = q;
-    }
-  }
-  return base;
-}
-
 // LDS as in gemm_gather_kernel: [ small image: msf*16 rows x PA ][ R: max(long image BN x PA, staging) ]; the two
 // offset tables lie in R before the first long image is written.
 // KIN: the innermost digit of the box is contracted.  ROWS_LONG / V: see the file header.
@@ -357,6 +304,12 @@ static bool scatter_enabled() {
   return on;
 }
 
+// TNH_GATHER_WIDE=0: the wide form of this entry is off together with the wide gather kernel
+static bool scatter_wide_enabled() {
+  static const bool on = []() { const char* e = getenv("TNH_GATHER_WIDE"); return !(e && e[0] == '0'); }();
+  return on;
+}
+
 template <int BN, bool ROWS_LONG, bool KIN, int V>
 static int launch_scatter(bool is_bf16, const ScatterArgs& q, size_t lds_bytes) {
   static const int attr_rc = []() -> int {
@@ -398,9 +351,13 @@ int gemm_gather_scatter(int dtype, int64_t Ms, int64_t K, int64_t Nl, const void
                         const char** name) {
   const char* why = nullptr;
   int bn = 0;
-  const bool shape_ok = scatter_enabled() && desc->kl_ext == 1 && Ms >= 4 && Ms <= 192 && K >= 8 && K <= 192 && K % 8 == 0 &&
-                        Nl >= 48 && lds % 8 == 0 && lds >= K && ((uintptr_t)S % 16) == 0 && ((uintptr_t)L % 8) == 0 &&
-                        Ms * lds < (int64_t(1) << 30);
+  // Ms > 192 or K > 192: the wide kernel (tnh_gemm_gather_scatter_wide.hip), which addresses S in 64 bits
+  const bool wide = Ms > 192 || K > 192;
+  const bool range_ok = wide ? scatter_wide_enabled() && Ms <= 256 && K <= 256 : Ms * lds < (int64_t(1) << 30);
+  const bool shape_ok = scatter_enabled() && desc->kl_ext == 1 && Ms >= 4 && range_ok && K >= 8 && K % 8 == 0 &&
+                        Nl >= 48 && lds % 8 == 0 && lds >= K && ((uintptr_t)S % 16) == 0 && ((uintptr_t)L % 8) == 0;
+  // (the descriptor check bounds the span of ONE box by 2^31 elements and its width by 256 indices, the wide kernel's
+  //  bound: the tensor itself may be larger)
   if (shape_ok) bn = gather_validate_cached(*desc, K, Nl, l_elems, &why);
   if (!bn) {
     set_error("tnh_gemm_gather_scatter: outside the kernel's range (%s)",
@@ -425,6 +382,7 @@ int gemm_gather_scatter(int dtype, int64_t Ms, int64_t K, int64_t Nl, const void
   q.a.K = (int)K;
   q.a.ntiles = (int)(Nl / bn);
   q.o = *out;
+  if (wide) return launch_gather_scatter_wide(bn, rows_long, desc->k_mask & 1, vec, dtype == TNH_BF16, q, name);
   const int Kp = (int)((K + 31) & ~31), PA = Kp * 2 + 16;
   const int msp = (q.a.Ms + 15) / 16 * 16;
   const size_t image = (size_t)bn * PA;          // >= 48 * 80 bytes: room for the two offset tables (256 x 8 bytes)

@@ -249,16 +249,17 @@ def _gather_descriptor_cached(shape, k_axes, max_box_k):
   return desc, bn, rows
 
 
-def _scatter_descriptor(shape, k_axes, out_strides, small_ext, small_strides):
+def _scatter_descriptor(shape, k_axes, out_strides, small_ext, small_strides, max_box_k=192):
   """see _scatter_descriptor_cached"""
   return _scatter_descriptor_cached(tuple(int(n) for n in shape), tuple(int(x) for x in k_axes),
                                     tuple(int(s) for s in out_strides), tuple(int(n) for n in small_ext),
-                                    tuple(int(s) for s in small_strides))
+                                    tuple(int(s) for s in small_strides), int(max_box_k))
 
 
 @functools.lru_cache(maxsize=512)
-def _scatter_descriptor_cached(shape, k_axes, out_strides, small_ext, small_strides):
-  """Output descriptor (tnh_scatter_desc, include/tnh.h) that goes with `_gather_descriptor(shape, k_axes)` for
+def _scatter_descriptor_cached(shape, k_axes, out_strides, small_ext, small_strides, max_box_k):
+  """Output descriptor (tnh_scatter_desc, include/tnh.h) that goes with `_gather_descriptor(shape, k_axes, max_box_k)`
+  (192: the narrow kernel's box bound; 256: the wide kernel's, which also bounds the box alone by 2^31 elements) for
   tnh_gemm_gather_scatter: `out_strides[ax]` = elements of the destination per index of the long tensor's axis `ax`
   (contracted axes: anything), `small_ext` / `small_strides` = the small operand's free axes in the order of its rows
   (outermost first) with their destination strides.  Returns (gather descriptor, scatter descriptor, BN, run_elements)
@@ -266,7 +267,7 @@ def _scatter_descriptor_cached(shape, k_axes, out_strides, small_ext, small_stri
   are not evenly spaced in the destination (those axes were pulled apart or swapped there).  `run_elements`: the
   contiguous run of the destination the kernel's stores are made of, 0 when its innermost axis is neither the small
   operand's innermost free axis nor the box's innermost free digit (the kernel refuses those)."""
-  plan = _gather_descriptor_cached(shape, k_axes, 192)
+  plan = _gather_descriptor_cached(shape, k_axes, max_box_k)
   if plan is None or plan[0].kl_ext != 1 or not 1 <= len(small_ext) <= _lib.SCATTER_MAX_SMALL_DIGITS:
     return None
   desc, bn, rows = plan
@@ -310,7 +311,10 @@ def _scatter_descriptor_cached(shape, k_axes, out_strides, small_ext, small_stri
   return desc, out, bn, run
 
 
-_VIEW_SCATTER_MIN_RUN = "24"       # default of HipBackend.view_scatter_min_run_bytes (profiles/view_scatter.md)
+# default of HipBackend.gather_scatter_wide_min_run_bytes ("off": None).  32 bytes, the shortest run there is at D = 16,
+# was 1.6-1.9 x faster than wide gather + K1 pass in every call (profiles/gather_scatter_wide.md)
+_GATHER_SCATTER_WIDE_MIN_RUN = "32"
+_VIEW_SCATTER_MIN_RUN = "24"      # default of HipBackend.view_scatter_min_run_bytes (profiles/view_scatter.md)
 
 
 def _cview_descriptor(ext_a, ext_b, order, keep_a, keep_b):
@@ -573,6 +577,12 @@ class HipBackend(BackendBase):
     _min_run = os.environ.get("TNH_GATHER_SCATTER_MIN_RUN", "24")      # "off": the contractors never ask
     self.gather_scatter_min_run_bytes = int(_min_run) if _min_run.isdigit() else None
     self.gather_scatter_launches = 0     # tnh_gemm_gather_scatter launches
+    # The wide form of the same entry (193 ... `gather_max_small` free tuples, tnh_gemm_gather_scatter_wide.hip) takes
+    # every explicit `result_order` it can store; `gather_scatter_wide_min_run_bytes` is the run from which
+    # `scatter_run_bytes` tells the CONTRACTORS about it (None: it answers 0 for that range) -- see
+    # profiles/gather_scatter_wide.md for where the value comes from.
+    _min_run = os.environ.get("TNH_GATHER_SCATTER_WIDE_MIN_RUN", _GATHER_SCATTER_WIDE_MIN_RUN)      # "off": never
+    self.gather_scatter_wide_min_run_bytes = int(_min_run) if _min_run.isdigit() else None
     # The same for the products of the 256 x 256 view GEMM (tnh_gemm_view_scatter; TNH_VIEW_SCATTER=0: off).
     # `view_scatter_min_run_bytes`: the contiguous run of the destination from which the backend takes the scattered
     # form at all (None: never) -- see profiles/view_scatter.md for where the value comes from.
@@ -1034,7 +1044,13 @@ class HipBackend(BackendBase):
     small = a if plan[1] else b
     if small.ptr % 16:
       return 0
-    return plan[0][3] * a.itemsize
+    run_bytes = plan[0][3] * a.itemsize
+    if min(_prod(a.shape[i] for i in free_a), _prod(b.shape[i] for i in free_b)) > 192:
+      # the wide form has a threshold of its own (None: the contractors never ask for it)
+      wide_min = self.gather_scatter_wide_min_run_bytes
+      if wide_min is None or run_bytes < wide_min:
+        return 0
+    return run_bytes
 
   def _scatter_plan(self, a, b, axes_a, axes_b, free_a, free_b, order):
     """The descriptors of `_tensordot_gather_scatter` for this product: ((gather descriptor, scatter descriptor, BN,
@@ -1044,7 +1060,9 @@ class HipBackend(BackendBase):
     k = _prod(a.shape[i] for i in axes_a)
     small_first = m <= n
     ms, nl = (m, n) if small_first else (n, m)
-    if not (64 < ms <= 192 and 16 <= k <= 192 and k % 8 == 0 and nl >= self.gather_min_rows):
+    # 193 ... `gather_max_small` free tuples: the wide form (tnh_gemm_gather_scatter_wide.hip), one box of up to 256
+    wide = 192 < ms <= self.gather_max_small
+    if not ((wide and 8 <= k <= 256) or (64 < ms <= 192 and 16 <= k <= 192)) or k % 8 or nl < self.gather_min_rows:
       return None
     long_ = b if small_first else a
     small = a if small_first else b
@@ -1065,14 +1083,16 @@ class HipBackend(BackendBase):
         used_s.append(i)
         small_strides.append(st)
     axes_l = axes_b if small_first else axes_a
-    plan = _scatter_descriptor(long_.shape, axes_l, out_strides, [small.shape[i] for i in used_s], small_strides)
+    plan = _scatter_descriptor(long_.shape, axes_l, out_strides, [small.shape[i] for i in used_s], small_strides,
+                               256 if wide else 192)
     if plan is None or plan[3] == 0 or plan[3] % 4:      # (run 0: an innermost axis the kernel does not store along)
       return None
     return plan, small_first, used_s, shape
 
   def _tensordot_gather_scatter(self, a, b, axes_a, axes_b, free_a, free_b, order):
     """One `tnh_gemm_gather_scatter` launch: the product `_tensordot_gather` takes (a small operand of 65 ... 192 free
-    tuples against ONE box of a long tensor read where it lies; here also with trailing contracted axes), written in
+    tuples, or 193 ... `gather_max_small` through the wide form, against ONE box of a long tensor read where it lies; here
+    also with trailing contracted axes), written in
     the axis order `order` over [free_a..., free_b...].  Only the small operand is permuted, to [its free axes in the
     order they have in the destination, contracted axes in the long tensor's memory order].  Or None (nothing
     launched): the caller runs the usual lowering and one transpose; results are bit-identical either way."""
