@@ -135,6 +135,13 @@ int tnh_strided_scatter(void* dst, const void* src, int rank,
  * f32 product, fp32 accumulate; error vs float64 no larger than the f32 MFMA kernel's, ~2x its
  * speed); TNH_F32_SPLIT=0 in the environment or the ":s0" knob of tnh_gemm_set_variant keeps every
  * F32 product on v_mfma_f32_32x32x2_f32.
+ * C64 / C128 products run on v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64 (tnh_gemm_complex.hip): the
+ * interleaved operands are read in place in any of the four storage forms and de-interleaved into planar LDS
+ * images, four MFMAs per 16 x 16 x 4 block (Cre += Ar Br - Ai Bi, Cim += Ar Bi + Ai Br), batched, any alpha /
+ * beta.  Kernel names mfma_c64_128x128x16 / mfma_c64_64x64x16 and mfma_c128_128x64x8 / mfma_c128_64x64x8; the
+ * small tile serves M <= 64, N <= 64 or fewer large tiles than CUs.  complex64 operands with an odd pitch, batch
+ * stride or an 8-byte aligned base are read with 8-byte loads in the same kernels.  "valu" of
+ * tnh_gemm_set_variant keeps the VALU kernel as the on-device second opinion.
  * Replaces AbstractBackend.tensordot / matmul / outer_product after the
  * transpose+reshape lowering (abstract_backend.py:27-38, 828-845, 202-205;
  * oracle numpy_backend.py:35-54, 609-612, 99-100; lowering spec
@@ -155,7 +162,9 @@ int tnh_gemm_ex(int in_dtype, int out_dtype, int transA, int transB, int64_t M,
  * src (element (k, n) at src[k * row_stride + n * col_stride], strides in complex elements):
  * [[re, im], [-im, re]] per element (conj != 0 conjugates first).  With it a complex product
  * with a row-major left operand is ONE real tnh_gemm on the interleaved images of A and C
- * (M x 2K times 2K x 2N): complex64 / complex128 tensordot on the f32 / f64 matrix cores. */
+ * (M x 2K times 2K x 2N): complex64 / complex128 tensordot on the f32 / f64 matrix cores (the "embedded"
+ * lowering, which also reaches split-K and the F32-on-bf16 kernels).  tnh_gemm with C64 / C128 operands needs
+ * no expansion: it multiplies the complex operands where they lie. */
 int tnh_complex_expand(void* dst, const void* src, int64_t K, int64_t N,
                        int64_t row_stride, int64_t col_stride, int conj, int dtype);
 
@@ -283,7 +292,8 @@ const char* tnh_gemm_last_kernel(void);
  * per-XCD M-grouped order with groups of 8 / 4 / 16 / 32 tile rows), ":p<d>" (bf16 pipeline variant; 6 = the
  * 4-wave kernel), ":s<d>" (F32-on-bf16-cores off / on), ":t<d>" (tail split), ":g<d>" (persistent grid), ":w<d>"
  * (cap on the K-walk form), ":l<d>" (lean main loop), ":e<d>" (next tile started under the draining epilogue
- * stores), ":n<d>" (non-temporal stores of large results): used by tests (second opinion) and bench.py / tools
+ * stores), ":n<d>" (non-temporal stores of large results), ":z<d>" (complex MFMA tile: 0 = the 64 x 64 tile, 1 = the
+ * large tile, whatever the shape): used by tests (second opinion) and bench.py / tools
  * (A/B); "auto" is the product setting and resets every knob.  None of them changes a result bit except ":p3"
  * (32x32x16 MFMA: another summation order) and ":s" (F32 products on the f32 matrix cores). */
 int tnh_gemm_set_variant(const char* name);

@@ -5,7 +5,9 @@
 //                         exact f32 fma chain), 128x128x16 tile, 4 waves.
 //   gemm_mfma_f64_kernel  f64, v_mfma_f64_16x16x4_f64, 64x64x16 tile.
 //   gemm_valu_kernel      any dtype incl. complex; 64x64x16 register-tiled VALU
-//                         kernel (also the on-device second opinion in tests).
+//                         kernel (integers, and the on-device second opinion in tests).
+//
+// complex64 / complex128 run on the matrix cores through tnh_gemm_complex.hip.
 //
 // The bf16/f16 speed path (LDS-DMA staged, 16x16x32 MFMA) lives in
 // tnh_gemm_bf16.hip and is selected here when its alignment rules hold.
@@ -20,17 +22,7 @@
 
 namespace tnh {
 
-struct GemmArgs {
-  const void* A;
-  const void* B;
-  void* C;
-  int64_t M, N, K;
-  int64_t rsA, csA, rsB, csB, ldc;
-  int64_t sA, sB, sC;
-  int out_dt;
-  double alpha, beta;  // C = alpha * A B + beta * C (real scalars; beta == 0 never reads C)
-  const int* run_if;   // non-null: the f32 kernels return at once unless *run_if != 0 (guard of the 3 x bf16 split)
-};
+// (GemmArgs: tnh_internal.h -- shared with tnh_gemm_complex.hip)
 
 // provided by tnh_gemm_bf16.hip
 extern int g_opt_raster, g_opt_phases, g_opt_tail, g_opt_persist, g_opt_kwalk, g_opt_lean, g_opt_epi, g_opt_nt;
@@ -1045,6 +1037,7 @@ static void launch_skinny(int ta, int tb, unsigned grid, const T* A, int64_t lda
 static thread_local bool g_in_splitk = false;   // re-entrancy guard of the split-K path
 static int g_variant = 0;  // 0 auto, 1 generic (mfma), 2 valu, 3 bf16_128, 4 bf16_256, 5 bf16_256pp,
                            // 6 bf16_ragged (auto shape), 7 .._128x128, 8 .._64x256, 9 .._256x64
+static int g_cplx_tile = -1;   // ":z<d>": complex MFMA tile, -1 by shape, 0 small (64 x 64), 1 large
 
 template <typename F>
 static int launch_batched(F launch, const GemmArgs& g0, int64_t batch, int BM, int BN) {
@@ -1082,6 +1075,7 @@ int tnh_gemm_set_variant(const char* full) {
   tnh::g_opt_epi = -1;
   tnh::g_opt_nt = -1;
   g_f32_split = -1;   // back to the environment's choice unless ":s<d>" follows
+  g_cplx_tile = -1;
   for (char* c = strchr(name, ':'); c != nullptr;) {
     *c = 0;
     char* next = strchr(c + 1, ':');
@@ -1094,6 +1088,7 @@ int tnh_gemm_set_variant(const char* full) {
     else if (c[1] == 'e') tnh::g_opt_epi = atoi(c + 2);
     else if (c[1] == 'n') tnh::g_opt_nt = atoi(c + 2);
     else if (c[1] == 's') g_f32_split = atoi(c + 2) ? 1 : 0;
+    else if (c[1] == 'z') g_cplx_tile = atoi(c + 2) ? 1 : 0;
     c = next;
   }
   if (!strcmp(name, "auto")) g_variant = 0;
@@ -1426,7 +1421,7 @@ int tnh_gemm_ex(int in_dtype, int out_dtype, int transA, int transB, int64_t M, 
   g.beta = beta;
   g.run_if = split_done ? g_split_flag : nullptr;
 
-  const bool use_valu = (g_variant == 2) || in_dtype == TNH_C64 || in_dtype == TNH_C128 || int_in;
+  const bool use_valu = (g_variant == 2) || int_in;
   const int esz_in = dtype_size(in_dtype);
   auto shifted = [&](int64_t b0) {
     GemmArgs h = g;
@@ -1445,6 +1440,16 @@ int tnh_gemm_ex(int in_dtype, int out_dtype, int transA, int transB, int64_t M, 
           return 0;
         },
         g, batch, 64, 64);
+  }
+  if (cplx_in) {
+    // complex64 / complex128 on the f32 / f64 matrix cores, interleaved operands read in place (tnh_gemm_complex.hip)
+    int BM = 0, BN = 0;
+    const char* name = nullptr;
+    const int large = gemm_complex_tile(in_dtype, M, N, batch, g_cplx_tile, &BM, &BN, &name);
+    g_last_kernel = name;
+    return launch_batched(
+        [&](const GemmArgs&, int64_t b0, dim3 grid) -> int { return gemm_complex_launch(in_dtype, large, shifted(b0), grid); },
+        g, batch, BM, BN);
   }
   if (in_dtype == TNH_F64 && M >= 128 && N >= 128 && ((M + 127) / 128) * ((N + 127) / 128) * batch >= 128 &&
       g_variant != 1) {

@@ -103,6 +103,27 @@ bool qr_panel16_supported(int dtype, int64_t m, int64_t n);
 size_t qr_panel16_work_bytes(int dtype, int64_t m, int64_t n);
 int qr_panel16(int dtype, int64_t m, int64_t n, const void* A, void* Q, void* R, void* work, int* status_host);
 
+// ---- arguments of the general strided-batched GEMM kernels (tnh_gemm.hip, tnh_gemm_complex.hip) ----
+// A(m,k) = A[m*rsA + k*csA], B(k,n) = B[k*rsB + n*csB] in elements of the input dtype; batch through blockIdx.z.
+struct GemmArgs {
+  const void* A;
+  const void* B;
+  void* C;
+  int64_t M, N, K;
+  int64_t rsA, csA, rsB, csB, ldc;
+  int64_t sA, sB, sC;
+  int out_dt;
+  double alpha, beta;  // C = alpha * A B + beta * C (real scalars; beta == 0 never reads C)
+  const int* run_if;   // non-null: the f32 kernels return at once unless *run_if != 0 (guard of the 3 x bf16 split)
+};
+
+// provided by tnh_gemm_complex.hip: complex64 / complex128 on v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64.
+// gemm_complex_tile picks the workgroup tile (force: -1 auto, 0 small, 1 large), returns 1 for the large one and
+// fills its extents and the kernel's name; gemm_complex_launch launches ONE grid of that tile (`g` already shifted
+// to the grid's first batch entry).
+int gemm_complex_tile(int dtype, int64_t M, int64_t N, int64_t batch, int force, int* BM, int* BN, const char** name);
+int gemm_complex_launch(int dtype, int large, const GemmArgs& g, dim3 grid);
+
 struct DimVec {
   int64_t v[TNH_MAX_RANK];
 };

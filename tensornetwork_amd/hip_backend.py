@@ -31,7 +31,7 @@ _PLAN_CODES = (_lib.BF16, _lib.F16, _lib.F32, _lib.F64, _lib.C64, _lib.C128)    
 class _TensordotPlan:
   """One lowering of the permute + ONE GEMM path (HipBackend._plan_generic)."""
   __slots__ = ("out_shape", "free_a", "free_b", "trans_a", "trans_b", "m", "n", "k", "lda", "ldb", "code", "out_code",
-               "out_bytes", "complex", "perm_a", "perm_b", "k1_a", "k1_b")
+               "out_bytes", "complex", "native", "perm_a", "perm_b", "k1_a", "k1_b")
 # promotion lattice for mixed-dtype binary ops / contractions (numpy's rules,
 # with bf16 treated like float16: any mix with a wider float wins).
 _RANK = {_lib.BF16: 0, _lib.F16: 0, _lib.F32: 1, _lib.F64: 2, _lib.C64: 3, _lib.C128: 4}
@@ -1227,7 +1227,7 @@ class HipBackend(BackendBase):
       try:
         key = (a._shape, b._shape, tuple(axes[0]), tuple(axes[1]), a._code,     # pylint: disable=protected-access
                None if hint_a is None else tuple(hint_a), None if hint_b is None else tuple(hint_b), allow_swap,
-               self.gather_gemm, self.absorb_transposes, self.half_output, self.gather_max_small)
+               self.gather_gemm, self.absorb_transposes, self.half_output, self.gather_max_small, self.complex_lowering)
         plan = self._td_plans.get(key)
       except TypeError:      # (an integer `axes`, unhashable entries: the general walk below)
         key = plan = None
@@ -1302,7 +1302,9 @@ class HipBackend(BackendBase):
   def _plan_generic(self, a_shape, b_shape, axes_a, axes_b, free_a, free_b, m, n, k, code, hint_a, hint_b):
     """The permute + ONE GEMM lowering of tensordot as data: which operands get a K1 permute (and where to), the
     storage forms handed to tnh_gemm, the result's shape and the order of the free axes in it.  A pure function of
-    its arguments and of `half_output` (part of the plan cache's key)."""
+    its arguments and of `half_output` / `complex_lowering` (parts of the plan cache's key)."""
+    if self.complex_lowering not in ("embedded", "native"):
+      raise ValueError(f"complex_lowering must be 'embedded' or 'native', got {self.complex_lowering!r}")
     nc = len(axes_a)
     nd_a, nd_b = len(a_shape), len(b_shape)
     # memory order of the contracted pairs on each side
@@ -1366,6 +1368,7 @@ class HipBackend(BackendBase):
     plan.out_code = _lib.F32 if (code in _HALF and self.half_output == "float32") else code
     plan.out_bytes = m * n * device_tensor._ITEMSIZE[plan.out_code]      # pylint: disable=protected-access
     plan.complex = code in _REAL_OF and 8 * m * n * k >= (1 << 18)
+    plan.native = plan.complex and self.complex_lowering == "native"
     plan.perm_a, plan.perm_b = perm_a, perm_b
     plan.k1_a = self._plan_permute(a_shape, perm_a, code)
     plan.k1_b = self._plan_permute(b_shape, perm_b, code)
@@ -1388,7 +1391,7 @@ class HipBackend(BackendBase):
         a = self.transpose(a, plan.perm_a)
       if plan.perm_b is not None:
         b = self.transpose(b, plan.perm_b)
-      if plan.complex:
+      if plan.complex and not plan.native:
         out = self._complex_gemm(a, b, bool(plan.trans_a), bool(plan.trans_b), plan.m, plan.n, plan.k)
       else:
         out = self._gemm(a, b, bool(plan.trans_a), bool(plan.trans_b), plan.m, plan.n, plan.k, plan.lda, plan.ldb, alias=alias)
@@ -1413,7 +1416,7 @@ class HipBackend(BackendBase):
         _lib.check(lib.tnh_permute(_vp(t), _vp(b), k1[2], k1[3], k1[4], k1[5]), "tnh_permute")
         b = t
     m, n, k = plan.m, plan.n, plan.k
-    if plan.complex:
+    if plan.complex and not plan.native:     # (native: the ONE tnh_gemm below, on the complex operands where they lie)
       out = self._complex_gemm(a, b, bool(plan.trans_a), bool(plan.trans_b), m, n, k).view(plan.out_shape)
       return out, list(plan.free_a), list(plan.free_b), False
     out = DeviceTensor._fresh(plan.out_shape, plan.out_code, plan.out_bytes,      # pylint: disable=protected-access
@@ -2200,6 +2203,9 @@ class HipBackend(BackendBase):
   kmajor_tile_walk = True        # tensordot: the size-dependent cost rule for a k-major `b` the whole-K-tile lean loop reads
   kmajor_tile_walk_max_pitch = 1 << 16       # (elements between consecutive k rows of such a `b`)
   kmajor_tile_walk_penalty_per_gb = 0.03     # (fraction of the product per GB of the operand beyond 0.6 GB)
+  complex_lowering = "embedded"   # planned complex tensordot (>= 2^18 flops): "embedded" = tnh_complex_expand + ONE real
+                                  # GEMM of M x 2N x 2K (`_complex_gemm`); "native" = ONE complex tnh_gemm on the operands
+                                  # where they lie (the mfma_c64_* / mfma_c128_* kernels; measured in profiles/complex_native.md)
   kmajor_inplace_penalty = 0.10  # tensordot: what reading a k-major operand in place costs the product (0: always in place
                                  # below inplace_max_bytes, the rule of rounds 2-4)
   inplace_strided_max_bytes = 4 << 30
