@@ -395,8 +395,12 @@ int tnh_wrap_int(void* dst, const void* src, int64_t n, int bits, int mode);
  * backends/numpy/decompositions.py:36 behind AbstractBackend.svd
  * (abstract_backend.py:79-137); the truncation bookkeeping (decompositions.py
  * :38-74) stays on the host. */
-/* dtype: TNH_F32 / TNH_F64 (block path for min(m, n) > 64) or TNH_C64 / TNH_C128 (unitary-rotation
- * 2-row kernel); S always has the REAL dtype of the same precision. */
+/* dtype: TNH_F32 / TNH_F64 / TNH_C64 / TNH_C128, all with the block path on the matrix cores for
+ * min(m, n) > 64 (complex: tnh_svd_block_complex.hip; the bound stayed at 64 after the measurement in
+ * profiles/svd_block_complex.md) and the 2-row kernel (complex: unitary plane rotations) below that or with
+ * TNH_SVD_BLOCK=0.  The complex block path reports rows below 4 eps |A|_F as zero singular values; exactly
+ * rank-deficient complex inputs get an orthonormal completion of the basis, as the real ones do.  S always has the
+ * REAL dtype of the same precision. */
 int tnh_svd_work_bytes(int dtype, int64_t m, int64_t n, size_t* nbytes);
 /* Two-phase form: tnh_svd_factor runs the sweeps and writes all singular
  * values to S; the host then applies the reference's truncation rule

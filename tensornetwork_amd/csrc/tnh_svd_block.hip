@@ -25,6 +25,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include "tnh_types.h"
+#include "tnh_svd_block_sched.h"
 
 namespace tnh {
 
@@ -33,74 +34,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // phase stamps (10 ns ticks of wall_clock64) of workgroup (0, 0) of the last gram / update launch, printed by TNH_SVD_TRACE=1
 __device__ int g_bj_phase[8];
-
-// Circle-method pairing of `n` (even) players: pair `i` of round `r` (a < b).
-__host__ __device__ __forceinline__ void bj_pair(int n, int r, int i, int& a, int& b) {
-  const int q = n - 1;
-  if (i == 0) {
-    a = q;
-    b = r % q;
-  } else {
-    a = (r + i) % q;
-    b = (r - i + q) % q;
-  }
-  if (a > b) {
-    const int t = a;
-    a = b;
-    b = t;
-  }
-}
-
-// Pairing of one GROUP of blocks in round r (k = pair index inside the group):
-//   shift == 0: circle method over the q blocks [abase, abase + q)                    (q / 2 pairs, q - 1 rounds)
-//   shift == 1: blocks [abase, abase + q) against [bbase, bbase + q), cyclic shifts   (q pairs, q rounds)
-// The GROUPED schedule (round 2, svd_block_sweeps) cuts the blocks into G = 2 or 4 parts and a sweep into phases in
-// which the G groups never touch the same block -- first the circle method inside every part, then, for every
-// matching of the parts, half-part x half-part products in two sub-phases -- every block pair once per sweep in
-// nb - 1 rounds, like the plain circle method.  Inside a phase each group runs its gram -> eig -> update chain on
-// its own stream with NO synchronisation between rounds: one group's latency-bound LDS eigensolve overlaps the
-// others' gram / update.
-struct BjGroup {
-  int shift, abase, bbase, q;
-};
-__host__ __device__ __forceinline__ void bj_pair_group(const BjGroup& g, int r, int k, int& a, int& b) {
-  if (g.shift == 0) {
-    bj_pair(g.q, r, k, a, b);
-    a += g.abase;
-    b += g.abase;
-  } else {
-    a = g.abase + k;
-    b = g.bbase + (k + r) % g.q;
-  }
-}
-
-// Phases of the grouped schedule for G = 2 or 4 groups (nb % (2 G) == 0): returns the phase count (3 or 7).
-struct BjPhase {
-  int rounds;
-  BjGroup g[4];
-};
-static int bj_build_schedule(int nb, int G, BjPhase* phases) {
-  int nphases = 0;
-  const int part = nb / G, hq = part / 2;      // blocks per part, per half part
-  BjPhase& p0 = phases[nphases++];
-  p0.rounds = part - 1;
-  for (int g = 0; g < G; ++g) p0.g[g] = BjGroup{0, g * part, 0, part};
-  // matchings of the parts: G = 2: (0,1); G = 4: (0,1)(2,3), (0,2)(1,3), (0,3)(1,2)
-  const int match2[1][1][2] = {{{0, 1}}};
-  const int match4[3][2][2] = {{{0, 1}, {2, 3}}, {{0, 2}, {1, 3}}, {{0, 3}, {1, 2}}};
-  const int nmatch = (G == 2) ? 1 : 3;
-  for (int m = 0; m < nmatch; ++m)
-    for (int t = 0; t < 2; ++t) {
-      BjPhase& ph = phases[nphases++];
-      ph.rounds = hq;
-      for (int mi = 0; mi < G / 2; ++mi) {
-        const int x = (G == 2) ? match2[0][mi][0] : match4[m][mi][0];
-        const int y = (G == 2) ? match2[0][mi][1] : match4[m][mi][1];
-        for (int u = 0; u < 2; ++u) ph.g[2 * mi + u] = BjGroup{1, x * part + u * hq, y * part + (u ^ t) * hq, hq};
-      }
-    }
-  return nphases;
-}
 
 // ---------------------------------------------------------------------- gram
 // grid (pairs, splits), 256 threads.  Wave w of split s covers the 8-column
@@ -839,8 +772,17 @@ size_t svd_block_scratch_bytes(int esz, int64_t P, int64_t Q) {
 }
 
 // auxiliary streams of the grouped round schedule (see svd_block_sweeps)
-static hipStream_t g_aux[3] = {nullptr, nullptr, nullptr};     // streams of groups 1 .. 3 of the grouped schedule
-static hipEvent_t g_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+int svd_block_group_streams(int G, hipStream_t** aux, hipEvent_t** ev) {
+  static hipStream_t g_aux[3] = {nullptr, nullptr, nullptr};     // streams of groups 1 .. 3 of the grouped schedule
+  static hipEvent_t g_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < G - 1; ++i)
+    if (!g_aux[i]) TNH_HIP(hipStreamCreateWithFlags(&g_aux[i], hipStreamNonBlocking));
+  for (int i = 0; i < G; ++i)
+    if (!g_ev[i]) TNH_HIP(hipEventCreateWithFlags(&g_ev[i], hipEventDisableTiming));
+  *aux = g_aux;
+  *ev = g_ev;
+  return TNH_OK;
+}
 
 // Sweeps until a whole sweep applies no rotation.  X: P x Q (ld Q), R: P x P.
 template <typename T>
@@ -895,26 +837,19 @@ int svd_block_sweeps(T* X, T* R, int64_t P, int64_t Q, char* scratch, int* flag,
   // is exhausted with two chains, more streams only add launches.  (Round 2 also tried the SAME circle round cut into G groups on G streams with a fork /
   // join per round, TNH_SVD_GROUPS: G = 2 / 3 / 4 -> 0.243 / 0.269 / 0.307 s against 0.216 -- the per-round events
   // cost more than the overlap returned.  This schedule needs cross-stream events only at the phase boundaries.)
-  int G = 1;
-  {
-    // two chains pay from 2048 rows on (f32 1024^2: 0.0206 s on one stream, 0.0216 s on two; f64 512^2: 0.0150 / 0.0174)
-    if (nb % 4 == 0 && nb >= 64) G = 2;
-    if (const char* envg = getenv("TNH_SVD_SCHED")) {
-      const int want = atoi(envg);
-      if (want == 1 || (want == 2 && nb % 4 == 0 && nb >= 8) || (want == 4 && nb % 8 == 0 && nb >= 16)) G = want;
-    }
-  }
+  // two chains pay from 2048 rows on (f32 1024^2: 0.0206 s on one stream, 0.0216 s on two; f64 512^2: 0.0150 / 0.0174)
+  int G = bj_choose_groups(nb);
   if (F64 && !eig64_new) G = 1;
   if (G > 1) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(stream(), &cap);
     if (cap != hipStreamCaptureStatusNone) G = 1;     // inside a graph capture: stay on one stream
   }
+  hipStream_t* g_aux = nullptr;
+  hipEvent_t* g_ev = nullptr;
   if (G > 1) {
-    for (int i = 0; i < G - 1; ++i)
-      if (!g_aux[i]) TNH_HIP(hipStreamCreateWithFlags(&g_aux[i], hipStreamNonBlocking));
-    for (int i = 0; i < G; ++i)
-      if (!g_ev[i]) TNH_HIP(hipEventCreateWithFlags(&g_ev[i], hipEventDisableTiming));
+    const int rc = svd_block_group_streams(G, &g_aux, &g_ev);
+    if (rc) return rc;
   }
   auto gstream = [&](int g) { return g == 0 ? stream() : g_aux[g - 1]; };
   // every stream has seen everything the others queued so far

@@ -2069,7 +2069,8 @@ class HipBackend(BackendBase):
         through the real embedding): band reduction, spectrum slicing for the values, inverse iteration for the KEPT
         vectors only, back-transformation.  Every call shape (max_singular_values, max_truncation_error, both, neither).
       * one-sided block Jacobi (K7; every other shape, and the fall-back): all singular values, then only the kept
-        vectors are emitted.  complex inputs use unitary plane rotations.
+        vectors are emitted.  complex inputs use unitary plane rotations, in 64-row blocks on the matrix cores for
+        min(m, n) > 64 like the real ones; exactly rank-deficient complex inputs get a completed basis.
 
     Which one ran is in `last_svd_path` after the call.  The band path reports numerically rank-deficient panels /
     unconverged vectors through a status word; the call then falls back to Jacobi, and a shape that reports twice in
