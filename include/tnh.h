@@ -470,7 +470,7 @@ int tnh_svd_band_last_stage1(void);
 int tnh_svd_block_schedule(int nb, int groups, int32_t* pairs_out, int* rounds_out);
 
 /* ---- K9: thin Householder QR --------------------------------------------------
- * A (m x n, row-major, f32 / f64) = Q (m x k) R (k x n), k = min(m, n); blocked
+ * A (m x n, row-major, f32 / f64 / complex64 / complex128) = Q (m x k) R (k x n), k = min(m, n); blocked
  * Householder (LAPACK geqrf + orgqr: same reflector sign convention, so R matches
  * np.linalg.qr up to rounding).  A is not modified; `work` holds
  * tnh_qr_work_bytes() bytes.
@@ -479,7 +479,14 @@ int tnh_svd_block_schedule(int nb, int groups, int32_t* pairs_out, int* rounds_o
  * non_negative_diagonal phase fix and the rq transposes stay on the host side of
  * the boundary, as in the reference.
  * f32 with m >= n >= 64, n % 16 == 0 runs on K7b's 16-wide panel kernels and reads ONE status word back (a
- * stream synchronisation per call); inside tnh_graph_begin / tnh_graph_end that path is not taken. */
+ * stream synchronisation per call); inside tnh_graph_begin / tnh_graph_end that path is not taken.
+ * TNH_C64 / TNH_C128: the same blocked scheme on row-major interleaved (re, im) elements, read where they lie (no real
+ * embedding), with LAPACK's zgeqrf + zungqr conventions: H = I - tau v v^H, beta = -sign(Re alpha) * sqrt(|alpha|^2 +
+ * xnorm^2) real, tau = ((beta - Re alpha) / beta, -Im alpha / beta), v = x / (alpha - beta), tau = 0 only when
+ * xnorm == 0 and Im alpha == 0 -- so R's diagonal is real, with LAPACK's sign.  Panels of 32 columns in compact WY form,
+ * one workgroup per panel up to 512 rows and one launch per column above (TNH_QR_TALL=0: always one workgroup), updates
+ * on the complex MFMA GEMM.  The complex dtypes read nothing back and never synchronise: capturable as they are.
+ * m == 0 or n == 0 returns TNH_OK. */
 int tnh_qr_work_bytes(int dtype, int64_t m, int64_t n, size_t* nbytes);
 int tnh_qr(int dtype, int64_t m, int64_t n, const void* A, void* Q, void* R,
            void* work);

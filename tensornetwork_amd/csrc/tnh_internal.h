@@ -103,6 +103,15 @@ bool qr_panel16_supported(int dtype, int64_t m, int64_t n);
 size_t qr_panel16_work_bytes(int dtype, int64_t m, int64_t n);
 int qr_panel16(int dtype, int64_t m, int64_t n, const void* A, void* Q, void* R, void* work, int* status_host);
 
+// K9 on complex64 / complex128 (tnh_qr_complex.hip): blocked Householder QR on interleaved (re, im) storage.
+// `tall`: panels taller than 512 rows run the multi-workgroup form.  No host read-back, no synchronisation.
+size_t qr_complex_work_bytes(int dtype, int64_t m, int64_t n);
+int qr_complex(int dtype, int64_t m, int64_t n, const void* A, void* Q, void* R, void* work, bool tall);
+// tnh_qr.hip, shared by the real and the complex path: W (32 x nt) = Vp^T C with Vp (mj x 32) and C (mj x nt, ldc), the
+// long K cut into up to QR_SPLITS slices (+ one remainder slice) in Wpart and summed in fixed order.
+constexpr int QR_SPLITS = 32;
+int qr_vt_times_c(int dt, const void* Vp, const void* C, int64_t ldc, int64_t mj, int64_t nt, void* W, void* Wpart);
+
 // ---- arguments of the general strided-batched GEMM kernels (tnh_gemm.hip, tnh_gemm_complex.hip) ----
 // A(m,k) = A[m*rsA + k*csA], B(k,n) = B[k*rsB + n*csB] in elements of the input dtype; batch through blockIdx.z.
 struct GemmArgs {

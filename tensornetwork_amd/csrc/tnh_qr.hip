@@ -14,6 +14,8 @@
 //                       W = V^T C, W <- T^T W, C <- C - V W   (tnh_gemm_ex, alpha/beta).
 //   Q (m x k) is then built like orgqr: Q = I_thin, panels applied last to first.
 //
+// complex64 / complex128 take the same entry points and run their own kernels (tnh_qr_complex.hip).
+//
 // Bound: the panel passes stream m_j x 32 elements through one CU (L2-resident), the
 // updates are skinny (K = 32) f32 / f64 MFMA GEMMs, HBM-bound at 2 * m_j * n_t elements each.
 #include <stdlib.h>
@@ -423,8 +425,8 @@ static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // long K.  One GEMM would run nt / 128 workgroups through the whole of K, so K is cut into up to
 // QR_SPLITS slices computed as ONE strided-batched GEMM (slice b -> Wpart[b]) and summed by the
 // K4 reduction kernel (fixed order: deterministic).
-constexpr int QR_SPLITS = 32;
-static int qr_vt_times_c(int dt, const void* Vp, const void* C, int64_t ldc, int64_t mj, int64_t nt, void* W,
+// (declared in tnh_internal.h with QR_SPLITS: the complex path calls it with conj(V) and a complex dtype)
+int qr_vt_times_c(int dt, const void* Vp, const void* C, int64_t ldc, int64_t mj, int64_t nt, void* W,
                          void* Wpart) {
   const int esz = dtype_size(dt);
   int64_t splits = mj / 256;
@@ -537,8 +539,13 @@ extern "C" {
 
 int tnh_qr_work_bytes(int dtype, int64_t m, int64_t n, size_t* nbytes) {
   TNH_REQUIRE(nbytes != nullptr, "null nbytes");
-  TNH_REQUIRE(dtype == TNH_F32 || dtype == TNH_F64, "tnh_qr supports f32 / f64 (got dtype %d)", dtype);
+  TNH_REQUIRE(dtype == TNH_F32 || dtype == TNH_F64 || dtype == TNH_C64 || dtype == TNH_C128,
+              "tnh_qr supports f32 / f64 / complex64 / complex128 (got dtype %d)", dtype);
   TNH_REQUIRE(m >= 0 && n >= 0, "negative extent");
+  if (dtype == TNH_C64 || dtype == TNH_C128) {
+    *nbytes = qr_complex_work_bytes(dtype, m, n);
+    return TNH_OK;
+  }
   size_t need = qr_layout(nullptr, dtype_size(dtype), m, n).total + 256;
   if (qr_panel16_supported(dtype, m, n)) {
     const size_t fast = qr_panel16_work_bytes(dtype, m, n);
@@ -554,10 +561,13 @@ int tnh_qr(int dtype, int64_t m, int64_t n, const void* A, void* Q, void* R, voi
     const char* env = getenv("TNH_QR_TALL");
     g_qr_tall = !(env && env[0] == '0');
   }
-  TNH_REQUIRE(dtype == TNH_F32 || dtype == TNH_F64, "tnh_qr supports f32 / f64 (got dtype %d)", dtype);
+  TNH_REQUIRE(dtype == TNH_F32 || dtype == TNH_F64 || dtype == TNH_C64 || dtype == TNH_C128,
+              "tnh_qr supports f32 / f64 / complex64 / complex128 (got dtype %d)", dtype);
   TNH_REQUIRE(m >= 0 && n >= 0, "negative extent");
   if (m == 0 || n == 0) return TNH_OK;
   TNH_REQUIRE(A && Q && R && work, "null pointer");
+  if (dtype == TNH_C64 || dtype == TNH_C128)   // interleaved complex: its own kernels (tnh_qr_complex.hip)
+    return qr_complex(dtype, m, n, A, Q, R, work, g_qr_tall);
   if (qr_panel16_supported(dtype, m, n) && !capturing()) {
     // 16-wide Cholesky-QR panels (one small kernel per panel instead of a launch per column); a numerically
     // rank-deficient panel is reported and the matrix goes through the column-by-column path below.  The report is a

@@ -2525,10 +2525,35 @@ class HipBackend(BackendBase):
           return np.stack(basis, axis=1)
     return None
 
+  complex_qr = "embedded"   # complex qr / rq: "embedded" = the real tnh_qr on the 2m x 2n embedding (`_qr_complex`);
+                            # "native" = ONE tnh_qr call on the interleaved complex matrix (tnh_qr_complex.hip; no
+                            # read-back, capturable; measured in profiles/qr_complex.md)
+  last_qr_path = None       # "real" / "embedded complex" / "native complex" after a qr / rq (or an svd's internal QR)
+
   def _qr_matrix(self, mat):
-    """Thin Householder QR of a device matrix (f32 / f64) -> (q (m, k), r (k, n))."""
+    """Thin Householder QR of a device matrix -> (q (m, k), r (k, n)); complex matrices follow `complex_qr`."""
     if mat.is_complex:
-      return self._qr_complex(mat)
+      if self.complex_qr not in ("embedded", "native"):
+        raise ValueError(f"complex_qr must be 'embedded' or 'native', got {self.complex_qr!r}")
+      if self.complex_qr == "embedded":
+        q, r = self._qr_complex(mat)
+        self.last_qr_path = "embedded complex"
+        return q, r
+      q, r = self._qr_device(mat)
+      # zgeqrf leaves R's diagonal real with LAPACK's sign: the same gauge step as the embedded path (diag(R) >= 0, a
+      # zero diagonal keeps +1; the factor is real, so it is its own conjugate on R's rows)
+      sgn = self.sign(self.real(self.diagonal(r)))
+      sgn = self._binary(_lib.OP_ADD, sgn, self._binary(_lib.OP_SUB, 1.0, self.abs(sgn)))
+      q = self._binary(_lib.OP_MUL, q, sgn)
+      r = self._binary(_lib.OP_MUL, self.reshape(sgn, (sgn.shape[0], 1)), r)
+      self.last_qr_path = "native complex"
+      return q, r
+    q, r = self._qr_device(mat)
+    self.last_qr_path = "real"
+    return q, r
+
+  def _qr_device(self, mat):
+    """One tnh_qr call on a device matrix of a dtype the kernel takes (f32 / f64 / complex64 / complex128)."""
     m, n = mat.shape
     k = min(m, n)
     nbytes = ctypes.c_size_t(0)
